@@ -22,9 +22,15 @@ torch.distributed.run from a parent that never touches the GPU):
                   each rank accumulates the winners it owns from its own shard, then
                   all_reduce(SUM) of the 24 accumulators.
   --mode weak     WEAK scaling: each rank registers its own 50M-vs-50M tile.
-At N > 1 the line also carries the two other modes under "alt_modes" (--no-alt skips them).
+At N > 1 a --full line also carries the two other modes under "alt_modes" (--no-alt skips them).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode slab|sharded|weak] [--n|--points 50000000]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the
+line.  --full adds the legs that take runs of their own: the CPU baseline (cpu_baseline; --no-cpu
+skips it) and, at N > 1, the two other modes (alt_modes; --no-alt skips them).  --dump-outputs DIR
+writes what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs below).
 
 The other BASELINE.json configs print the same JSON contract with --config (one step = one
 pass of that config's hot path over one batch; every rank runs its own batch, so N > 1 is weak
@@ -71,8 +77,12 @@ def parse():
     ap.add_argument("--halo", type=float, default=2.0, help="slab mode: target halo (m), >= rmax + motion")
     ap.add_argument("--cpu-n", type=int, default=2_000_000, help="CPU baseline sample (all threads)")
     ap.add_argument("--cpu-iters1", type=int, default=3, help="CPU baseline iterations on 1 thread")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="N > 1: skip the alt_modes runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the CPU baseline and, at N > 1, the alt_modes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="--full at N > 1: skip the alt_modes runs")
     ap.add_argument("--c5-points", type=int, default=200_000_000,
                     help="--config C5: points per GPU (the 200M-pt scene fits one GPU)")
     ap.add_argument("--c5-check", type=int, default=0,
@@ -135,6 +145,34 @@ def pmc_traffic(workload):
                 tot += e["launches"] * (e["fetch_bytes_avg"] + (e["write_bytes_avg"] or 0.0))
         return tot / iters, os.path.relpath(f, ROOT)
     return None
+
+
+DUMP_BYTES = 60_000_000    # --dump-outputs: budget of all the arrays together (under 64 MB with the headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each of `arrays` (name -> tensor, ndarray or scalar) as
+    <path>/<name>.npy, floating types wider than fp32 and integers as float64 (exact below 2^53),
+    the rest as float32.  The files share DUMP_BYTES equally; an array over its share is written
+    as a fixed sample of its leading-axis rows (seeded by the array's length only, ascending, the
+    same rows in every run and every build), so two runs compare file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        t = t.detach().reshape(1) if t.dim() == 0 else t.detach()
+        wide = (not t.dtype.is_floating_point) or t.element_size() > 4
+        row_bytes = max(1, t[0].numel()) * (8 if wide else 4) if t.shape[0] else 1
+        keep = share // row_bytes
+        if t.shape[0] > keep:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(t.shape[0])
+            rows = torch.sort(torch.randint(0, t.shape[0], (keep,), generator=g)).values
+            t = t[rows.to(t.device)]
+        t = t.to(torch.float64 if wide else torch.float32).cpu().contiguous()
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
 
 
 def cpu_info():
@@ -361,7 +399,7 @@ def main():
                 kernel["launches"] += nl
                 kernel["fallback"] += st.get("fallback", 0.0)
                 info["guard_ok"] = info["guard_ok"] and ok
-            result["T"], result["err"], result["nq"] = T, err, eng.icp.q.shape[0]
+            result["T"], result["err"], result["ok"], result["nq"] = T, err, ok, eng.icp.q.shape[0]
             eng.close()
 
         for _ in range(warmup):
@@ -390,7 +428,7 @@ def main():
             "icp_iter_per_s": args.iters * steps / dt,
             "exchange_ms_per_iter": max_over_ranks(exch_ms),
             "guard_ok": bool(max_over_ranks(0.0 if info["guard_ok"] else 1.0) == 0.0),
-            "T": result["T"], "err": result["err"],
+            "T": result["T"], "err": result["err"], "last_guard_ok": result["ok"],
             "kernel_avg_ms": kernel["ms"] / max(kernel["launches"], 1),
             "units_per_launch": result["nq"],
             "queries_all_ranks": sum_over_ranks(float(result["nq"])),
@@ -405,13 +443,19 @@ def main():
 
     main_rec = run_mode(args.mode, args.steps, args.warmup)
     alt = {}
-    if world > 1 and not args.no_alt:
+    if args.full and world > 1 and not args.no_alt:
         for m in ("slab", "sharded", "weak"):
             if m != args.mode:
                 r = run_mode(m, max(1, args.steps), 1)
-                alt[m] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items() if k not in ("T",)}
+                alt[m] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()
+                          if k not in ("T", "last_guard_ok")}
                 alt[m]["T_err_vs_truth"] = float(np.abs(r["T"] - T_true).max())
 
+    if rank == 0 and args.dump_outputs:
+        # what run_slab_dev / run_target_sharded_dev returned to rank 0 in the last timed step
+        # (err, T, guard_ok); slab and sharded modes return the same on every rank
+        dump_outputs(args.dump_outputs, {"T": main_rec["T"], "err": main_rec["err"],
+                                         "guard_ok": float(main_rec["last_guard_ok"])})
     if rank == 0:
         r = main_rec
         traffic = pmc_traffic({"n": n, "world": world, "mode": args.mode})
@@ -469,7 +513,8 @@ def main():
             },
             "alt_modes": alt or None,
             "build_id": _lib.load().pcp_build_id().decode(),  # SHA-1 of the libpcp sources (provenance)
-            "cpu_baseline": None if (args.no_cpu or world > 1) else cpu_baseline(args, T_true, synth),
+            "cpu_baseline": cpu_baseline(args, T_true, synth) if (args.full and not args.no_cpu and world == 1)
+            else None,
         }
         print(json.dumps(line), flush=True)
     ctx.close()

@@ -1,8 +1,8 @@
 """bench.py --config C1 | C2 | C3 | C5: the other BASELINE.json configs, one JSON line each with
 the bench.py contract (value = whole-job throughput over the timed steps, max over ranks;
 roofline of the dominant kernel from HIP events on the stream it runs on; cpu_baseline = the
-oracle restatement on a bounded sample, rank 0 at N = 1 only).  Every rank runs its own batch
-(weak scaling, no collective).  Inputs are resident in HBM before the timed region.
+oracle restatement on a bounded sample, rank 0 at N = 1 with --full only).  Every rank runs its
+own batch (weak scaling, no collective).  Inputs are resident in HBM before the timed region.
 
 Algorithmic bytes / flops per unit follow SURVEY.md §8(d):
   C2  8 flops per (query, target) pair (the K=4 contraction) -> fp32 MFMA peak
@@ -152,14 +152,23 @@ def street_aos48(n, seed, device):
     return c.view(torch.uint8).reshape(n, 48).contiguous()
 
 
-def run_steps(step, steps, warmup, barrier):
+KEEP = {}  # --dump-outputs: what the last timed step returned (name -> tensor), else empty
+
+
+def _kept(last, **arrays):
+    """A step's outputs, kept for --dump-outputs when this is the last timed step."""
+    if last:
+        KEEP.update(arrays)
+
+
+def run_steps(step, steps, warmup, barrier, keep=False):
     for _ in range(warmup):
         step(False)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        step(True)
+    for i in range(steps):
+        step(True, keep and i == steps - 1)
     torch.cuda.synchronize()
     barrier()
     return time.perf_counter() - t0
@@ -176,12 +185,13 @@ def cfg_c1(ctx, args, rank, timer):
     q = torch.from_numpy(np.random.default_rng(1002 + rank).uniform(-10, 10, (100_000, 3))).to(ctx.device)
     n = len(pts)
 
-    def step(timed):
+    def step(timed, last=False):
         def run():
             vox = ops.voxel_filter(ctx, cloud, 0.1)
             ix = ops.GridIndex(ctx, vox, stride_bytes=48)
             out = ops.knn(ix, q, 1)
             ix.close()
+            _kept(last, knn_idx=out[0], knn_d2=out[1])
             return out
         timer(run) if timed else run()
 
@@ -211,9 +221,10 @@ def cfg_c2(ctx, args, rank, timer):
     t = synth.uniform_cube(n, 2001 + 1000 * rank, half=50.0, device=ctx.device)
     q = synth.uniform_cube(n, 2002 + 1000 * rank, half=50.0, device=ctx.device)
 
-    def step(timed):
+    def step(timed, last=False):
         fn = lambda: ops.knn_bruteforce(ctx, t, q, 8)
-        timer(fn) if timed else fn()
+        out = timer(fn) if timed else fn()
+        _kept(last, knn_idx=out[0], knn_d2=out[1])
 
     flops = 8.0 * n * n
     info = {"unit": "Mqueries/s", "units_per_step": n, "dtype": "f32",
@@ -246,13 +257,14 @@ def cfg_c3(ctx, args, rank, timer):
     ntimer = Timer()
     state = {}
 
-    def step(timed):
+    def step(timed, last=False):
         def run():
             vox = ops.voxel_filter(ctx, cloud, 0.05)
             ix = ops.GridIndex(ctx, vox, stride_bytes=48)
             nrm = ntimer(lambda: ops.normals_knn(ix, 32)) if timed else ops.normals_knn(ix, 32)
             state["m"] = vox.shape[0]
             ix.close()
+            _kept(last, normals=nrm)
             return nrm
         timer(run) if timed else run()
 
@@ -322,13 +334,14 @@ def cfg_c5(ctx, args, rank, timer):
     btimer = Timer()
     state = {}
 
-    def step(timed):
+    def step(timed, last=False):
         def run():
             ix = btimer(lambda: ops.H16Index(ctx, xyz, cell_size=R)) if timed else ops.H16Index(ctx, xyz, cell_size=R)
             fn = lambda: ix.radius_normals(R, n_owned=n_owned, global_id=gid)
             offs, idx, nrm = ktimer(fn) if timed else fn()
             state["nnz"] = idx.numel()
             ix.close()
+            _kept(last, row_offsets=offs, row_indices=idx, normals=nrm)
             return nrm
         timer(run) if timed else run()
 
@@ -442,8 +455,13 @@ def main(args):
 
     timer = Timer()
     step, info, cpu = {"C1": cfg_c1, "C2": cfg_c2, "C3": cfg_c3, "C5": cfg_c5}[args.config](ctx, args, rank, timer)
-    dt = run_steps(step, args.steps, args.warmup, barrier)
+    dump = getattr(args, "dump_outputs", None) if rank == 0 else None
+    dt = run_steps(step, args.steps, args.warmup, barrier, keep=bool(dump))
     dt = reduce(dt, dist.ReduceOp.MAX if world > 1 else None)
+    if dump:  # rank 0's batch (every rank runs its own)
+        import bench
+        bench.dump_outputs(dump, KEEP)
+        KEEP.clear()
     units = info.get("units_all_ranks_per_step", info["units_per_step"] * world) * args.steps
     per_rank = None
     if "per_rank_fn" in info and world > 1:
@@ -485,7 +503,7 @@ def main(args):
         "build_id": ctx.lib.pcp_build_id().decode(),  # SHA-1 of the libpcp sources (provenance)
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and getattr(args, "full", False) and not args.no_cpu:
         line["cpu_baseline"] = _cpu_meta(cpu())
     if rank == 0:
         print(json.dumps(line), flush=True)
