@@ -210,6 +210,12 @@ int pcp_remove_duplicate(pcp_ctx* ctx, const void* in_aos48_dev, int64_t n, int 
  * points dropped as non-finite get {0,0,0,1}); sign: largest-|.| component positive. */
 int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* index, int k, pcp_plane* out_dev,
                     int64_t n_out);
+/* Which search passes the last pcp_normals_knn on this context used (diagnostic).
+ * *tile_deferred: queries the tile pass could not certify and handed on (-1: sparse grid,
+ * no tile ran); *far_queries: queries answered by the exact wave-per-query pass.  Both 0
+ * when the call returned before searching (k <= 3 after clamping, empty index, error).
+ * pcp_normals_knn itself stays asynchronous; this call waits for the stream. */
+int pcp_normals_knn_last_deferred(pcp_ctx* ctx, int64_t* tile_deferred, int64_t* far_queries);
 
 /* F3: CalculateFeature::calculate_plan_parameter_rpca(cloud, radius (unused), Pr, epi)
  * (calculate_feature.cpp:208-368; the pipeline's normals entry, static.cpp:17) over the

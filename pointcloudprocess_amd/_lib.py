@@ -81,6 +81,7 @@ SIGNATURES = [
     ("pcp_pose_loop_closure", _i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64]),
     ("pcp_remove_duplicate", _i32, [_vp, _vp, _i64, _i32, _f32, _vp, _P(_i64)]),
     ("pcp_normals_knn", _i32, [_vp, _vp, _i32, _vp, _i64]),
+    ("pcp_normals_knn_last_deferred", _i32, [_vp, _P(_i64), _P(_i64)]),
     ("pcp_icp_create", _i32, [_vp, _vp, _vp, _sz, _i64, _P(_vp)]),
     ("pcp_icp_check_sizes", _i32, [_i64, _i64]),
     ("pcp_icp_destroy", _i32, [_vp]),

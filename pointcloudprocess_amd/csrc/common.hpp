@@ -24,6 +24,12 @@ struct pcp_ctx {
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
     uint32_t bf_fallback = 0;  // queries of the last pcp_knn_bruteforce that needed the exact scan
+    // deferral counts of the last pcp_normals_knn (pcp_normals_knn_last_deferred): two device
+    // words the call copies its list counters into, stream-ordered; allocated on first use.
+    // nrm_mode: 0 nothing searched, 1 dense grid {tile's list, near pass's list}, 2 sparse
+    // grid {near pass's list, unused}
+    uint32_t* nrm_deferred = nullptr;
+    int nrm_mode = 0;
     // look-back scan state (scan.hip): per-tile status words tagged with the call's epoch, so
     // no clearing pass is needed per call; [tiles] u64 status, then the tile counter and total
     uint64_t* scan_status = nullptr;

@@ -924,6 +924,13 @@ __global__ void k_plane_default(pcp_plane* out, int64_t n) {
         out[i] = pcp_plane{0.f, 0.f, 0.f, 0.f, 1.f, 0.f};  // rpca's N <= 3 branch (:353-361)
 }
 
+// the call's deferral counters into the context's two words (pcp_normals_knn_last_deferred);
+// b null: the second word is unused
+__global__ void k_keep_deferred(const uint32_t* a, const uint32_t* b, uint32_t* out) {
+    out[0] = *a;
+    out[1] = b ? *b : 0u;
+}
+
 // queries = the indexed points themselves, walked in the index's spatial order
 // `in` (near pass only): the sorted positions to process (the tiled kernel's uncertified
 // queries), or every point when in.list is null
@@ -1880,6 +1887,7 @@ int pcp_radius_fill(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t q
 
 int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, int64_t n_out) {
     PCP_TRY(check_f64_index(ctx, ix));
+    ctx->nrm_mode = 0;
     if (k <= 0 || n_out < 0 || (n_out > 0 && !out)) return set_error(ctx, PCP_ERR_ARG, "pcp_normals_knn: bad arguments");
     if (n_out < ix->n_in) return set_error(ctx, PCP_ERR_CAPACITY, "pcp_normals_knn: n_out < cloud size");
     const int kk = (int)(k < ix->n ? k : ix->n);
@@ -1888,6 +1896,7 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     if (n_out > 0) hipLaunchKernelGGL(k_plane_default, dim3(blocks_for(n_out)), dim3(kB), 0, ctx->stream, out, n_out);
     if (ix->n == 0 || kk <= 3) return PCP_OK;  // rpca's N > 3 guard (calculate_feature.cpp:237)
+    if (!ctx->nrm_deferred) PCP_HIP(ctx, hipMalloc(&ctx->nrm_deferred, 2 * sizeof(uint32_t)));
     const double mc = cell_margin64(ix->g);
     const double4* pts = (const double4*)ix->pts;
     FarBuf fb;
@@ -1951,7 +1960,10 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
             default: LAUNCH_TILE(32); break;
         }
 #undef LAUNCH_TILE
+        hipLaunchKernelGGL(k_keep_deferred, dim3(1), dim3(1), 0, ctx->stream, fb.f.count,
+                           near_pass ? fb2.f.count : nullptr, ctx->nrm_deferred);
         PCP_LAUNCH_CHECK(ctx);
+        ctx->nrm_mode = 1;
 #if PCP_NORMALS_STATS
         {
             unsigned long long h[24];
@@ -1985,7 +1997,28 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
         default: LAUNCH_NRM(32); break;
     }
 #undef LAUNCH_NRM
+    hipLaunchKernelGGL(k_keep_deferred, dim3(1), dim3(1), 0, ctx->stream, fb.f.count, (const uint32_t*)nullptr,
+                       ctx->nrm_deferred);
     PCP_LAUNCH_CHECK(ctx);
+    ctx->nrm_mode = 2;
+    return PCP_OK;
+}
+
+int pcp_normals_knn_last_deferred(pcp_ctx* ctx, int64_t* tile_deferred, int64_t* far_queries) {
+    if (!ctx || !tile_deferred || !far_queries) return PCP_ERR_ARG;
+    *tile_deferred = *far_queries = 0;
+    if (!ctx->nrm_mode) return PCP_OK;
+    uint32_t h[2] = {0, 0};
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    PCP_HIP(ctx, hipMemcpyAsync(h, ctx->nrm_deferred, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->nrm_mode == 1) {
+        *tile_deferred = h[0];
+        *far_queries = h[1];
+    } else {
+        *tile_deferred = -1;
+        *far_queries = h[0];
+    }
     return PCP_OK;
 }
 

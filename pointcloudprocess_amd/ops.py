@@ -291,6 +291,15 @@ def normals_knn(index, k):
     return out[:n_out]
 
 
+def normals_knn_last_deferred(ctx):
+    """(tile_deferred, far_queries) of the last normals_knn on ctx: the queries the tile pass
+    handed on (-1 on a sparse grid, where no tile runs) and those the exact wave-per-query
+    pass answered.  Waits for the stream (diagnostic)."""
+    t, f = C.c_int64(), C.c_int64()
+    ctx.check(ctx.lib.pcp_normals_knn_last_deferred(ctx.h, C.byref(t), C.byref(f)))
+    return t.value, f.value
+
+
 POINT_PROPERTY = np.dtype([("normal_x", "<f4"), ("normal_y", "<f4"), ("normal_z", "<f4"), ("pad", "<u4"),
                            ("distance", "<f8"), ("curvature", "<f8"), ("point_id", "<i4"),
                            ("segment_id", "<i4"), ("dis_from_point_plane", "<f4"), ("pad2", "<u4")])
