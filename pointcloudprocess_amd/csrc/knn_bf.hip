@@ -10,8 +10,9 @@
 // best fp32 scores of each (row, class) in registers.  The union of the 16 class lists is
 // then re-ranked with the exact fp64 d2 and CERTIFIED: every target outside it has
 // score >= tau = min_c(L-th best of class c), so d2 >= |q|^2 + tau - E (E bounds the fp32
-// rounding).  A query whose k-th exact d2 is not below that bound is re-done by an exact
-// fp64 scan (k_bf_fallback) -- the result is exact either way.
+// rounding, with an absolute term for scales at which fp32 underflows).  A query whose k-th
+// exact d2 is not below that bound, or whose scores may have overflowed fp32, is re-done by an
+// exact fp64 scan (k_bf_fallback) -- the result is exact either way.
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -53,6 +54,17 @@ constexpr int kBfUnroll = PCP_BF_UNROLL;
 // vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8])
 constexpr int kWaitVm0 = 0x0F70;
 constexpr int kPerThread = kTile / kBlock;
+// Absolute part of the fp32 score error bound: E's relative terms assume no fp32 underflow.  A
+// cast, product or sum that lands below FLT_MIN (gradually or flushed) is off by up to FLT_MIN
+// instead: 5 such operations in |p|^2, 4 in the fma chain, 1 in the threshold subtraction, and
+// the casts of p and q move the score by at most 7 each while |p| + |q| <= 1 (beyond that the
+// relative terms cover them) -- 24, rounded up.
+constexpr double kEabs = 32.0 * FLT_MIN;
+// Above this (|p|max + |q|)^2 a finite target's fp32 |p|^2 or q.p may overflow: it is then never
+// ranked (+inf / NaN score) although its exact d2 is finite, so tau says nothing about it and
+// the row goes to the exact scan uncertified.  Below it every fp32 intermediate is finite:
+// |p|^2 + 2 |q| |p| <= (|p| + |q|)^2 < 2^120.
+constexpr double kRangeMax = 0x1p120;
 
 __device__ __forceinline__ const double* dptr(const double* base, size_t stride, int64_t i) {
     return (const double*)((const char*)base + (size_t)i * stride);
@@ -223,7 +235,7 @@ __global__ __launch_bounds__(kBlock, W) void k_bf_mfma(BfArgs a) {
         }
         for (int o = 32; o > 0; o >>= 1) q2 = fmax(q2, __shfl_xor(q2, o, 64));
         const double qn = sqrt(q2);
-        ew = (float)(a.E2 * (a.pmax + qn) * (a.pmax + qn) * 1.001);
+        ew = (float)(a.E2 * (a.pmax + qn) * (a.pmax + qn) * 1.001 + kEabs);
     }
     const bool use_theta = a.kk <= 16;
 
@@ -399,12 +411,21 @@ __global__ __launch_bounds__(kBlock, W) void k_bf_mfma(BfArgs a) {
                 }
                 if (qfin && a.kk > 0) {
                     const double qn = sqrt(qx * qx + qy * qy + qz * qz);
-                    const double e = a.E2 * (a.pmax + qn) * (a.pmax + qn);
+                    const double s2 = (a.pmax + qn) * (a.pmax + qn);
+                    const double e = a.E2 * s2 + kEabs;
                     const double lb = (qx * qx + qy * qy + qz * qz) + (double)tau - e;
-                    if (!(kth < lb)) a.fb[atomicAdd(a.fb_count, 1u)] = (int32_t)qi;
+                    if (!(kth < lb) || !(s2 < kRangeMax)) a.fb[atomicAdd(a.fb_count, 1u)] = (int32_t)qi;
                 }
             }
         }
+}
+
+// no finite target at all: every row is padding
+__global__ void k_bf_empty(int32_t* oidx, double* od2, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        oidx[i] = -1;
+        od2[i] = INFINITY;
+    }
 }
 
 // exact fp64 scan for uncertified queries: one 256-thread block per query, per-lane
@@ -462,13 +483,13 @@ extern "C" {
 
 int pcp_knn_bruteforce(pcp_ctx* ctx, const double* t, size_t tstride, int64_t nt, const double* q, size_t qstride,
                        int64_t nq, int k, int32_t* oidx, double* od2) {
+    if (ctx) ctx->bf_fallback = 0;  // a rejected call searched nothing
     if (!ctx || nt < 0 || nq < 0 || k <= 0 || (nt > 0 && !t) || (nq > 0 && (!q || !oidx || !od2)))
         return set_error(ctx, PCP_ERR_ARG, "pcp_knn_bruteforce: bad arguments");
     if (k > 32) return set_error(ctx, PCP_ERR_UNSUPPORTED, "pcp_knn_bruteforce: k=%d > 32 not supported yet", k);
     if (nt >= ((int64_t)1 << 31)) return set_error(ctx, PCP_ERR_ARG, "pcp_knn_bruteforce: < 2^31 targets");
     if (tstride == 0) tstride = 3 * sizeof(double);
     if (qstride == 0) qstride = 3 * sizeof(double);
-    ctx->bf_fallback = 0;
     if (nq == 0) return PCP_OK;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -493,7 +514,14 @@ int pcp_knn_bruteforce(pcp_ctx* ctx, const double* t, size_t tstride, int64_t nt
         if (e != hipSuccess) rc = hip_fail(ctx, e, "bf targets", __FILE__, __LINE__);
         for (unsigned b = 0; b < npb; b++) { pmax2 = std::fmax(pmax2, h[2 * b]); nfin += h[2 * b + 1]; }
     }
-    if (!rc) {
+    if (!rc && nfin == 0.0) {
+        // nt == 0 or no finite target: k_bf_mfma stages a whole tile before it looks at nt, and
+        // t4 holds none here -- the rows are all padding, written without it
+        hipLaunchKernelGGL(k_bf_empty, dim3(grid_for(nq * k, 256, 1024)), dim3(256), 0, st, oidx, od2, nq * (int64_t)k);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = hip_fail(ctx, e, "k_bf_empty", __FILE__, __LINE__);
+    } else if (!rc) {
         BfArgs a;
         a.t4 = t4; a.t = t; a.tstride = tstride; a.nt = nt;
         a.q = q; a.qstride = qstride; a.nq = nq;
