@@ -282,11 +282,19 @@ int pcp_icp_create_with_target(pcp_ctx* ctx, const float* target_dev, size_t tar
 /* not an ablation: keep 16-byte cache records although the target fits the 12-byte form
  * (< 2^26 - 2 points); only before the handle's first launch.  Results are identical. */
 #define PCP_ICP_OPT_WIDE_CACHE 128
-/* not an ablation: device-pose launches after the first replay ONE captured HIP graph of the
- * verify .. fallback section instead of enqueueing its five kernels (results are identical).
+/* not an ablation: device-pose launches from the handle's third on replay ONE captured HIP graph
+ * of the verify .. fallback section instead of enqueueing its five kernels (results are identical;
+ * the second launch still runs the plain search kernel, PCP_ICP_OPT_NO_LOOKAHEAD below).
  * Off by default: the device loop is host-asynchronous, so enqueueing is never what the GPU
  * waits for, and the replayed section measured 0.5 % slower per iteration. */
 #define PCP_ICP_OPT_GRAPH 256
+/* not an ablation: switch the look-ahead search centre off.  By default a query that has to be
+ * searched again is searched around a point ahead of it on its path, c = T_c q with
+ * T_c = T_t + beta (T_t - T_{t-1}), so that its cache certifies more of the coming launches
+ * (DESIGN.md 5.1); beta comes from the ratio of the last two steps and is 0 at the first two
+ * launches and whenever the step did not shrink.  With this flag beta = 0 on every launch and
+ * the search kernels are the plain ones.  Results are identical either way. */
+#define PCP_ICP_OPT_NO_LOOKAHEAD 512
 int pcp_icp_set_options(pcp_icp* icp, int oct_lanes_first, int oct_lanes_list, int ring_lanes, int ablate);
 int pcp_icp_destroy(pcp_icp* icp);
 /* One iteration at pose T (row-major 4x4 double, cast to fp32 for the kernel):
@@ -368,6 +376,10 @@ int pcp_icp_kernel_ms(pcp_ctx* ctx, pcp_icp* icp, double* ms, int* launches);
 int pcp_icp_last_fallback(const pcp_icp* icp, int64_t* n);
 /* Queries of the last pcp_icp_step that the verify pass could not settle (searched). */
 int pcp_icp_last_searched(const pcp_icp* icp, int64_t* n);
+/* The look-ahead of the handle's last launch (waits for it): beta, and the largest offset
+ * |c - q_t| (metres) over the corners of the target grid's box grown by rmax.  Both 0 when the
+ * launch searched around q_t itself. */
+int pcp_icp_last_lookahead(const pcp_icp* icp, double* beta, double* max_offset_m);
 
 /* PointCloudHelper::get_rot_icp (point_cloud_helper.cpp:75-166) on AoS48 clouds:
  * joint centroid (sequential fold over src ++ temp; non-finite points skipped unless both

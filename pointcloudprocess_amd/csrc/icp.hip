@@ -78,6 +78,7 @@ struct pcp_icp {
     float graph_r2 = 0.f;            // the rmax^2 it was captured with
     bool graph_off = false;          // capture failed: plain launches
     bool graph = false;              // PCP_ICP_OPT_GRAPH
+    bool no_look = false;            // PCP_ICP_OPT_NO_LOOKAHEAD: beta = 0, the plain search kernels
 };
 
 namespace pcp {
@@ -108,6 +109,7 @@ struct IcpArgs {
     int64_t nchunks;
     float R[9], t[3];
     float Rp[9], tq[3]; // the previous launch's pose (verify pass)
+    float Rc[9], tc[3]; // the look-ahead map T_c of this launch (k_pose_set): where the searches centre
     float r2;
     float cert2;        // certified radius^2 of the 2x2x2 octant search
     float rho;          // octant half-width in cell units (0.5 - margin)
@@ -156,6 +158,14 @@ __device__ __forceinline__ void load_pose(IcpArgs& a) {
         for (int k = 0; k < 3; k++) a.t[k] = a.pose[9 + k];
     }
 }
+// the look-ahead map (pose block words kPoseC ..): equal to the pose when beta = 0
+constexpr int kPoseStep = 25, kPoseBeta = 26, kPoseOff = 27, kPoseC = 28, kPoseWords = 40;
+__device__ __forceinline__ void load_pose_c(IcpArgs& a) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) a.Rc[k] = a.pose[kPoseC + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) a.tc[k] = a.pose[kPoseC + 9 + k];
+}
 __device__ __forceinline__ void load_prev_pose(IcpArgs& a) {
 #pragma unroll
     for (int k = 0; k < 9; k++) a.Rp[k] = a.pose[12 + k];
@@ -173,6 +183,13 @@ __device__ __forceinline__ void xform(const IcpArgs& a, const float4 q, float& x
     x = __fmaf_rn(a.R[2], q.z, __fmaf_rn(a.R[1], q.y, __fmaf_rn(a.R[0], q.x, a.t[0])));
     y = __fmaf_rn(a.R[5], q.z, __fmaf_rn(a.R[4], q.y, __fmaf_rn(a.R[3], q.x, a.t[1])));
     z = __fmaf_rn(a.R[8], q.z, __fmaf_rn(a.R[7], q.y, __fmaf_rn(a.R[6], q.x, a.t[2])));
+}
+// the same chain under the look-ahead map: the search centre c (the verify pass rebuilds exactly
+// this from the launch's history slot)
+__device__ __forceinline__ void xform_c(const IcpArgs& a, const float4 q, float& x, float& y, float& z) {
+    x = __fmaf_rn(a.Rc[2], q.z, __fmaf_rn(a.Rc[1], q.y, __fmaf_rn(a.Rc[0], q.x, a.tc[0])));
+    y = __fmaf_rn(a.Rc[5], q.z, __fmaf_rn(a.Rc[4], q.y, __fmaf_rn(a.Rc[3], q.x, a.tc[1])));
+    z = __fmaf_rn(a.Rc[8], q.z, __fmaf_rn(a.Rc[7], q.y, __fmaf_rn(a.Rc[6], q.x, a.tc[2])));
 }
 // the same expression under the previous launch's pose
 __device__ __forceinline__ void xform_prev(const IcpArgs& a, const float4 q, float& x, float& y, float& z) {
@@ -894,6 +911,20 @@ __device__ __forceinline__ int wave_max_u(int v) {
     v = max(v, __shfl_xor(v, 32, 64));
     return v;
 }
+// A look-ahead search ranks every candidate twice: by its distance to the search centre c (Top3P:
+// what is cached) and by its distance to the query at this launch's pose q_t (Min2P: this
+// launch's own result).  Min2P keeps the 2 smallest packed keys at q_t.  When their d2 bits differ
+// above the low byte the first is the strict minimum over the scanned points, so the exact
+// (d2, index) winner; otherwise (a tie or a near-tie within 256 ulps) the query is left to the
+// exact fallback pass.
+struct Min2P {
+    uint32_t u0 = kKeyMax, u1 = kKeyMax;
+    __device__ __forceinline__ void consider(float qx, float qy, float qz, const float4 p, uint32_t v) {
+        const uint32_t x = (__float_as_uint(icp_d2(qx, qy, qz, p)) & ~0xffu) | v;
+        u1 = umed3(u0, u1, x);
+        u0 = min(u0, x);
+    }
+};
 struct Top3P {
     uint32_t t0 = kKeyMax, t1 = kKeyMax, t2 = kKeyMax, t3 = kKeyMax;
     __device__ __forceinline__ void consider(float qx, float qy, float qz, const float4 p, uint32_t v) {
@@ -910,10 +941,13 @@ struct Top3P {
     // query, lane `sub` of the group takes list entries sub, sub + G, sub + 2G, ...: the group's
     // loads of one step are G consecutive records of a row (one or two cache lines), so a wave
     // instruction touches ~64 / G lines instead of 64 (what bounds the sparse search lists).
-    template <int G>
+    // LOOK: (qx, qy, qz) is the search centre c, and every candidate is also ranked at the query's
+    // current position (tx, ty, tz) into m2 (same loads, a second distance).
+    template <int G, bool LOOK = false>
     __device__ __forceinline__ void scan4(const float4* pts, uint32_t sent, const uint32_t (&rs)[4],
                                           const uint32_t (&rn)[4], uint32_t Lw, float qx, float qy, float qz,
-                                          uint32_t sub) {
+                                          uint32_t sub, Min2P* m2 = nullptr, float tx = 0.f, float ty = 0.f,
+                                          float tz = 0.f) {
         const uint32_t c1 = rn[0], c2 = c1 + rn[1], c3 = c2 + rn[2], L = c3 + rn[3];
         const uint32_t o0 = rs[0], o1 = rs[1] - c1, o2 = rs[2] - c2, o3 = rs[3] - c3;
         auto lv = [=](uint32_t v) { return v * G + sub; };  // this lane's v-th list entry
@@ -929,13 +963,19 @@ struct Top3P {
             for (int u = 0; u < U; u++) B[u] = ld16(pts, addr(v + U + u));
             __builtin_amdgcn_sched_barrier(0);  // keep B's loads ahead of A's keys
 #pragma unroll
-            for (int u = 0; u < U; u++) consider(qx, qy, qz, A[u], lv(v + u));
+            for (int u = 0; u < U; u++) {
+                consider(qx, qy, qz, A[u], lv(v + u));
+                if constexpr (LOOK) m2->consider(tx, ty, tz, A[u], lv(v + u));
+            }
             if (v + U >= Lg) break;
 #pragma unroll
             for (int u = 0; u < U; u++) A[u] = ld16(pts, addr(v + 2 * U + u));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int u = 0; u < U; u++) consider(qx, qy, qz, B[u], lv(v + U + u));
+            for (int u = 0; u < U; u++) {
+                consider(qx, qy, qz, B[u], lv(v + U + u));
+                if constexpr (LOOK) m2->consider(tx, ty, tz, B[u], lv(v + U + u));
+            }
         }
     }
     // the G lanes of a query merge their 4 smallest keys: per butterfly step the 4 smallest of
@@ -982,6 +1022,7 @@ struct OctResult {
     float wx = 0.f, wy = 0.f, wz = 0.f;
     uint32_t c0 = ~0u, c1 = ~0u, c2 = ~0u;  // the cache: positions of the 3 kept points
     float dnext = INFINITY;    // lower bound on the d2 of every scanned point not kept
+    bool uniq = false;         // look-ahead scans: d0 / win are this launch's exact winner
 };
 
 __device__ __forceinline__ void take_exact(OctResult& o, const float4 p, uint32_t pos, float qx, float qy, float qz,
@@ -1108,6 +1149,90 @@ __device__ __forceinline__ OctResult octant_packed(const IcpArgs& a, const uint3
     return o;
 }
 
+// Look-ahead form of the two scans: the cache (c0..c2, dnext) ranks by the distance to the search
+// centre (cx, cy, cz); the winner (d0, win, w*) is this launch's own result, the nearest scanned
+// point to the query's current position (qx, qy, qz).  o.uniq: d0 is exact and strictly below every
+// other scanned point's d2 (packed form) or the (d2, index) winner (compare-swap form); without it
+// d0 is only a lower bound and the query goes to the fallback.  The scatter / key kernels and the
+// fallback read this launch's winner from the cache, so a winner that is not among the 3 nearest
+// to c takes the third's place, and that point's distance then bounds the uncached ones.
+template <int G>
+__device__ __forceinline__ OctResult octant_packed_la(const IcpArgs& a, const uint32_t (&rs)[4],
+                                                      const uint32_t (&rn)[4], uint32_t Lw, float cx, float cy, float cz,
+                                                      float qx, float qy, float qz, uint32_t sub) {
+    Top3P k;
+    Min2P m;
+    k.scan4<G, true>(a.tp, a.ntp, rs, rn, Lw, cx, cy, cz, sub, &m, qx, qy, qz);
+    k.merge_group<G>();
+#pragma unroll
+    for (int s = 1; s < G; s <<= 1) {  // the group's 2 smallest (keys of one query are distinct)
+        const uint32_t o0 = Top3P::xor_lane(m.u0, s), o1 = Top3P::xor_lane(m.u1, s);
+        const uint32_t hi = max(m.u0, o0);
+        m.u0 = min(m.u0, o0);
+        m.u1 = min(hi, min(m.u1, o1));
+    }
+    const uint32_t c1 = rn[0], c2 = c1 + rn[1], c3 = c2 + rn[2], L = c3 + rn[3];
+    const uint32_t o0 = rs[0], o1 = rs[1] - c1, o2 = rs[2] - c2, o3 = rs[3] - c3;
+    OctResult o;
+    o.c0 = k.t0 != kKeyMax ? cat_addr_l(k.t0 & 0xffu, c1, c2, c3, L, o0, o1, o2, o3, a.ntp) : ~0u;
+    o.c1 = k.t1 != kKeyMax ? cat_addr_l(k.t1 & 0xffu, c1, c2, c3, L, o0, o1, o2, o3, a.ntp) : ~0u;
+    o.c2 = k.t2 != kKeyMax ? cat_addr_l(k.t2 & 0xffu, c1, c2, c3, L, o0, o1, o2, o3, a.ntp) : ~0u;
+    o.dnext = k.t3 == kKeyMax ? INFINITY : __uint_as_float(k.t3 & ~0xffu);
+    const bool any = m.u0 != kKeyMax;
+    o.uniq = any && (m.u1 & ~0xffu) > (m.u0 & ~0xffu);
+    o.d0 = any ? __uint_as_float(m.u0 & ~0xffu) : INFINITY;
+    if (any) {
+        const uint32_t w = cat_addr_l(m.u0 & 0xffu, c1, c2, c3, L, o0, o1, o2, o3, a.ntp);
+        if (w != o.c0 && w != o.c1 && w != o.c2) {  // (then 4 or more were scanned: t2 is a real key)
+            o.c2 = w;
+            o.dnext = __uint_as_float(k.t2 & ~0xffu);
+        }
+        const float4 p = ld16(a.tp, w);  // every lane of the group: one address
+        o.win = w;
+        o.wx = p.x;
+        o.wy = p.y;
+        o.wz = p.z;
+        if (o.uniq) o.d0 = icp_d2(qx, qy, qz, p);
+    }
+    return o;
+}
+
+// running (d2, index) winner of the compare-swap scan at the query's current position
+__device__ __noinline__ OctResult octant_exact_la(const IcpArgs& a, uint32_t rs0, uint32_t rs1, uint32_t rs2,
+                                                  uint32_t rs3, uint32_t rn0, uint32_t rn1, uint32_t rn2, uint32_t rn3,
+                                                  float cx, float cy, float cz, float qx, float qy, float qz) {
+    const uint32_t rs[4] = {rs0, rs1, rs2, rs3}, rn[4] = {rn0, rn1, rn2, rn3};
+    struct {
+        Top3 b;
+        Best w{INFINITY, 0x7fffffff, ~0u, 0.f, 0.f, 0.f};
+    } t;
+    for (int r = 0; r < 4; r++)
+        for (uint32_t k = rs[r]; k < rs[r] + rn[r]; k++) {
+            const float4 p = ld16(a.tp, k);
+            t.b.consider(cx, cy, cz, p, k);
+            t.w.consider(qx, qy, qz, p, k);
+        }
+    OctResult o;
+    o.c0 = t.b.p0;
+    o.c1 = t.b.p1;
+    o.c2 = t.b.p2;
+    o.dnext = t.b.d3;
+    o.uniq = t.w.bk != ~0u;
+    if (o.uniq) {
+        if (t.w.bk != o.c0 && t.w.bk != o.c1 && t.w.bk != o.c2) {
+            o.c2 = t.w.bk;
+            o.dnext = t.b.d2;
+        }
+        t.w.fetch(a.tp);
+        o.d0 = t.w.bd;
+        o.win = t.w.bk;
+        o.wx = t.w.px;
+        o.wy = t.w.py;
+        o.wz = t.w.pz;
+    }
+    return o;
+}
+
 // compare-swap scan (a chunk with a list of 256 or more candidates)
 __device__ __noinline__ OctResult octant_exact(const IcpArgs& a, uint32_t rs0, uint32_t rs1, uint32_t rs2, uint32_t rs3,
                                                uint32_t rn0, uint32_t rn1, uint32_t rn2, uint32_t rn3, float qx, float qy,
@@ -1133,7 +1258,14 @@ __device__ __noinline__ OctResult octant_exact(const IcpArgs& a, uint32_t rs0, u
 // chunk is 64 / G queries.  G > 1 serves the sparse search lists of later launches, whose
 // lanes no longer share candidate lines.
 constexpr int kOctW = kIcpBlock / 64;
-template <int G>
+//
+// LOOK (the search lists of a handle with the look-ahead on): the block, its rows, the cache and D
+// are taken around the centre c = T_c q (k_pose_set), which lies ahead on the query's path, so the
+// cached ball outlives more of the coming steps.  The certificate of the verify pass is geometry
+// about c alone, whatever c is.  This launch's own result is still the exact winner at q_t = T_t q:
+// the nearest scanned point to q_t, certified by q_t's distance to the faces of the block that was
+// scanned (a block around c may hold q_t off-centre, or not at all: then the fallback decides).
+template <int G, bool LOOK>
 __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list, int64_t n,
                                            double (*s_acc)[kAcc]) {
     constexpr int kW = kOctW;
@@ -1162,11 +1294,20 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
             qn = ldq(a, in_);
         }
         float qx = 0.f, qy = 0.f, qz = 0.f, fx = 0.f, fy = 0.f, fz = 0.f, dout = 0.f;
+        float cx = 0.f, cy = 0.f, cz = 0.f, delta = 0.f;  // LOOK: the centre, |q_t - c| rounded up
         int bx = 0, by = 0, bz = 0;
         bool outside = true;
         if (valid) {
             xform(a, qraw, qx, qy, qz);
-            fx = cell_f<float>(g, qx, 0), fy = cell_f<float>(g, qy, 1), fz = cell_f<float>(g, qz, 2);
+            if constexpr (LOOK) {
+                xform_c(a, qraw, cx, cy, cz);
+                const float ex = qx - cx, ey = qy - cy, ez = qz - cz;
+                const float e2 = __fmaf_rn(ez, ez, __fmaf_rn(ey, ey, ex * ex));
+                delta = e2 > 0.f ? sqrtf(e2) * 1.00001f + 1e-7f : 0.f;
+            } else {
+                cx = qx, cy = qy, cz = qz;
+            }
+            fx = cell_f<float>(g, cx, 0), fy = cell_f<float>(g, cy, 1), fz = cell_f<float>(g, cz, 2);
             bx = (int)floorf(fx - a.rho), by = (int)floorf(fy - a.rho), bz = (int)floorf(fz - a.rho);
             // a query farther than rmax from the grid's box (a target-sharded rank: the queries
             // of the other shards) is settled "no correspondence" without a scan, with D = that
@@ -1175,7 +1316,9 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
             const float oy = fmaxf(fmaxf(-fy, fy - (float)g.n[1]), 0.f);
             const float oz = fmaxf(fmaxf(-fz, fz - (float)g.n[2]), 0.f);
             dout = fmaxf(sqrtf(__fmaf_rn(oz, oz, __fmaf_rn(oy, oy, ox * ox))) - a.mc, 0.f) * g.hf;
-            outside = dout * dout > a.r2 * 1.0001f;
+            // (LOOK: dout is c's distance to the box; q_t is at least dout - delta from it)
+            const float dq = LOOK ? fmaxf(dout - delta, 0.f) : dout;
+            outside = dq * dq > a.r2 * 1.0001f;
         }
         const bool scanq = !outside;
         uint32_t rs[4], rn[4];
@@ -1184,10 +1327,18 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
         const uint32_t Lw = (uint32_t)__builtin_amdgcn_readfirstlane(wave_max_u((int)len));  // wave-uniform
         OctResult o;
         if (!(a.dbg & kDbgNoScan)) {
-            if (Lw <= kMaxOctList)
-                o = octant_packed<G>(a, rs, rn, Lw, qx, qy, qz, sub);
-            else
-                o = octant_exact(a, rs[0], rs[1], rs[2], rs[3], rn[0], rn[1], rn[2], rn[3], qx, qy, qz);
+            if constexpr (LOOK) {
+                if (Lw <= kMaxOctList)
+                    o = octant_packed_la<G>(a, rs, rn, Lw, cx, cy, cz, qx, qy, qz, sub);
+                else
+                    o = octant_exact_la(a, rs[0], rs[1], rs[2], rs[3], rn[0], rn[1], rn[2], rn[3], cx, cy, cz, qx,
+                                        qy, qz);
+            } else {
+                if (Lw <= kMaxOctList)
+                    o = octant_packed<G>(a, rs, rn, Lw, qx, qy, qz, sub);
+                else
+                    o = octant_exact(a, rs[0], rs[1], rs[2], rs[3], rn[0], rn[1], rn[2], rn[3], qx, qy, qz);
+            }
         }
         bool settled = false, found = false;
         if (valid) {
@@ -1197,17 +1348,34 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
                                         fminf(fy - (float)by, (float)(by + 2) - fy)),
                                   fminf(fz - (float)bz, (float)(bz + 2) - fz)) - a.mc;
             const float rr = m * g.hf;
-            const float cert2 = fmaxf(a.cert2, rr * rr * (1.f - 2e-5f));
-            found = o.d0 <= a.r2;
-            settled = (found ? (o.d0 < o.dnext && o.d0 <= cert2) : a.r2 <= cert2) || outside ||
-                      (a.dbg & kDbgNoFallback);
+            if constexpr (LOOK) {
+                // q_t's own distance to the faces of the block scanned (around c): every target
+                // nearer to q_t than that was scanned.  Not positive: q_t is outside the block.
+                const float tx = cell_f<float>(g, qx, 0), ty = cell_f<float>(g, qy, 1), tz = cell_f<float>(g, qz, 2);
+                const float mt = fminf(fminf(fminf(tx - (float)bx, (float)(bx + 2) - tx),
+                                             fminf(ty - (float)by, (float)(by + 2) - ty)),
+                                       fminf(tz - (float)bz, (float)(bz + 2) - tz)) - a.mc;
+                const float rt = mt * g.hf;
+                const float cert2 = mt > 0.f ? rt * rt * (1.f - 2e-5f) : -1.f;
+                // o.d0 is exact with o.uniq, else a lower bound on every scanned point's d2
+                found = o.uniq && o.d0 <= a.r2;
+                settled = (found ? o.d0 <= cert2 : (o.d0 > a.r2 && a.r2 <= cert2)) || outside ||
+                          (a.dbg & kDbgNoFallback);
+            } else {
+                const float cert2 = fmaxf(a.cert2, rr * rr * (1.f - 2e-5f));
+                found = o.d0 <= a.r2;
+                settled = (found ? (o.d0 < o.dnext && o.d0 <= cert2) : a.r2 <= cert2) || outside ||
+                          (a.dbg & kDbgNoFallback);
+            }
             // the cache: the 3 nearest; settled: D bounds every uncached point for the verify
             // pass.  Unsettled: the fallback pass (which overwrites the cache) gets the
             // octant's first uncached d2 instead.
             // (unsettled: the message is the octant's first uncached distance, rounded down)
             const float D = outside ? dout * 0.9999f
                                     : (settled ? fminf(sqrtf(o.dnext), (m > 0.f ? m : 0.f) * g.hf) * 0.9999f
-                                               : sqrtf(o.dnext) * 0.99999f);
+                                               // (LOOK: dnext is measured from c; the fallback's skip
+                                               // proof needs the bound at q_t)
+                                               : fmaxf(sqrtf(o.dnext) - delta, 0.f) * 0.99999f);
             if (lead) cache_store(a, i, o.c0, o.c1, o.c2, D, a.launch);
         }
         // ---- fallback list (ballot + mbcnt, no atomics) and accumulators
@@ -1240,23 +1408,25 @@ __device__ __forceinline__ int octant_lanes(int64_t n, int64_t nq) {
 // MINW: the first (dense) launch runs at PCP_OCT_WAVES waves/SIMD; the search lists of later
 // launches at PCP_OCT_WAVES_LIST, whose larger register budget measured faster on them.  A grid
 // smaller than the partial rows / list segments sized for the first launch zeroes the rest.
-template <int MINW>
+// LOOK: the look-ahead form (octant_run), for the search lists unless PCP_ICP_OPT_NO_LOOKAHEAD.
+template <int MINW, bool LOOK>
 __global__ void __launch_bounds__(kIcpBlock, MINW) k_icp_octant(IcpArgs a, const int32_t* list,
                                                                  const uint32_t* list_n) {
     load_pose(a);
+    if constexpr (LOOK) load_pose_c(a);
     __shared__ double s_acc[kOctW][kAcc];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int64_t n = list ? (int64_t)*list_n : a.nq;
     if (lane < kAcc) s_acc[wid][lane] = 0.0;
     const int G = a.oct_g ? a.oct_g : octant_lanes(n, a.nq);  // uniform over the grid
     if (G == 1)
-        octant_run<1>(a, list, n, s_acc);
+        octant_run<1, LOOK>(a, list, n, s_acc);
     else if (G == 2)
-        octant_run<2>(a, list, n, s_acc);
+        octant_run<2, LOOK>(a, list, n, s_acc);
     else if (G == 4)
-        octant_run<4>(a, list, n, s_acc);
+        octant_run<4, LOOK>(a, list, n, s_acc);
     else
-        octant_run<8>(a, list, n, s_acc);
+        octant_run<8, LOOK>(a, list, n, s_acc);
     write_wave_partials(s_acc, a.partials + (int64_t)blockIdx.x * kAcc);
     for (int64_t r = gridDim.x + blockIdx.x; r < a.nb_fast; r += gridDim.x)
         if (threadIdx.x < kAcc) a.partials[r * kAcc + threadIdx.x] = 0.0;
@@ -1303,7 +1473,8 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
         int64_t i = 0;
         if (valid) {
             i = a.ring_all ? j : list[j];
-            xform(a, ldq(a, i), qx, qy, qz);
+            const float4 qraw = ldq(a, i);
+            xform(a, qraw, qx, qy, qz);
             // provisional: the cache's best (refreshed by the search pass), an upper bound
             const CacheRec cd = cache_load(a, i);
             const CacheBest cbst = cache_best(a.tp, cd, qx, qy, qz);
@@ -1315,7 +1486,8 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
             // the search pass left this launch's octant message: the 4th smallest distance of
             // its octant (rounded down).  Above the cached best, every octant point tied with
             // that best is cached, so the cached best IS the octant's (d2, index) winner and its
-            // cells need no rescan.
+            // cells need no rescan.  (A look-ahead search scanned the block around its centre
+            // c = T_c q, and its message is already weakened by |q_t - c| to a bound at q_t.)
             const bool skip_oct = !a.ring_all && cd.slot == (a.launch & a.hist_mask) && cd.D * cd.D > cbst.bd;
             bool done = false;
             if (!a.ring_all) {
@@ -1327,7 +1499,12 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
                 const float fx = cell_f<float>(g, qx, 0), fy = cell_f<float>(g, qy, 1), fz = cell_f<float>(g, qz, 2);
                 const int cx = (int)floorf(fx), cy = (int)floorf(fy), cz = (int)floorf(fz);
                 const float lx = fx - (float)cx, ly = fy - (float)cy, lz = fz - (float)cz;
-                const int bxo = (int)floorf(fx - a.rho), byo = (int)floorf(fy - a.rho), bzo = (int)floorf(fz - a.rho);
+                // the block the octant pass scanned: chosen from c (= q_t when beta = 0)
+                float ccx, ccy, ccz;
+                xform_c(a, qraw, ccx, ccy, ccz);
+                const int bxo = (int)floorf(cell_f<float>(g, ccx, 0) - a.rho),
+                          byo = (int)floorf(cell_f<float>(g, ccy, 1) - a.rho),
+                          bzo = (int)floorf(cell_f<float>(g, ccz, 2) - a.rho);
                 const float inv_h2 = g.inv_hf * g.inv_hf;
                 const float gxl = sq_gap(lx, a.mc), gxr = sq_gap(1.f - lx, a.mc);
                 for (int dz = -1; dz <= 1; dz++) {
@@ -1341,8 +1518,9 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
                         const float gyz = gz2 + sq_gap(axis_gap<float>(y, cy, ly), a.mc);
                         int xlo = max(cx - 1, 0), xhi = min(cx + 1, g.n[0] - 1);
                         if (skip_oct && y >= byo && y <= byo + 1 && z >= bzo && z <= bzo + 1) {
-                            if (bxo == cx - 1) xlo = max(xlo, cx + 1);
-                            else xhi = min(xhi, cx - 1);
+                            // cells [bxo, bxo + 1] were scanned: cut them off the end they cover
+                            if (bxo <= xlo) xlo = max(xlo, bxo + 2);
+                            else if (bxo + 1 >= xhi) xhi = min(xhi, bxo - 1);
                         }
                         if (xlo == cx - 1 && gyz + gxl > lim) xlo = cx;
                         if (xhi == cx + 1 && gyz + gxr > lim) xhi = cx;
@@ -1378,6 +1556,7 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
 __global__ void __launch_bounds__(kIcpBlock, PCP_RING_WAVES) k_icp_ring(IcpArgs a, double* partials,
                                                                         const int32_t* list, const uint32_t* list_n) {
     load_pose(a);
+    load_pose_c(a);
     constexpr int kW = kIcpBlock / 64;
     __shared__ double s_acc[kW][kAcc];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -1806,14 +1985,72 @@ __host__ __device__ double det3(const double M[9]) {
 struct HostPose {
     float R[9], t[3];
 };
-__global__ void k_pose_set(const double* T, HostPose hp, float* pose, float* hist, uint32_t launch) {
+// The look-ahead map.  ICP steps are almost collinear and shrink geometrically (ratio r per
+// launch), so a query's remaining path from q_t is about (q_t - q_{t-1}) r / (1 - r) along the
+// last step.  A search centred at c = T_c q, T_c = T_t + beta (T_t - T_{t-1}) with
+// beta = alpha r / (1 - r), puts the cached ball around the path still to come instead of around
+// its start.  T_c is an affine map, written to this launch's history slot (where the verify pass
+// rebuilds c) and beside the pose (where the search kernels read it).  Exactness never depends on
+// it: the certificate holds for any centre; beta only decides how many later searches there are.
+// The step's size is its largest displacement over the corners of `box`, the target grid's box
+// grown by rmax (it holds every query that can have a correspondence); beta = 0 at the first two
+// launches (no ratio yet), when the step did not shrink (a pose jump included), and it is cut so
+// that no corner's offset exceeds cap.
+struct LookAhead {
+    float lo[3], hi[3];  // the box
+    float alpha, cap;    // fraction of the predicted remaining path; largest offset (m)
+    int off;             // PCP_ICP_OPT_NO_LOOKAHEAD
+};
+#ifndef PCP_LOOK_ALPHA
+#define PCP_LOOK_ALPHA 0.5f
+#endif
+#ifndef PCP_LOOK_R1  // step ratio assumed at launch 1, which has no previous step (0: no look-ahead there)
+#define PCP_LOOK_R1 0.f
+#endif
+constexpr float kLookAlpha = PCP_LOOK_ALPHA, kLookCap = 0.02f, kLookRmax = 0.9f, kLookR1 = PCP_LOOK_R1;
+__global__ void k_pose_set(const double* T, HostPose hp, LookAhead la, float* pose, float* hist, uint32_t launch) {
     *(uint32_t*)(pose + 24) = launch;
     for (int k = 0; k < 12; k++) pose[12 + k] = pose[k];
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) pose[3 * r + c] = T ? (float)T[4 * r + c] : hp.R[3 * r + c];
         pose[9 + r] = T ? (float)T[4 * r + 3] : hp.t[r];
     }
-    for (int k = 0; k < 12; k++) hist[k] = pose[k];
+    // this step's displacement of a point y (target frame): y - T_{t-1} T_t^-1 y = M y + v
+    double A[9], B[9], ta[3], tb[3], Ai[9], BA[9], v[3];
+    for (int k = 0; k < 9; k++) { A[k] = pose[k]; B[k] = pose[12 + k]; }
+    for (int k = 0; k < 3; k++) { ta[k] = pose[9 + k]; tb[k] = pose[21 + k]; }
+    const double det = det3(A);
+    Ai[0] = A[4] * A[8] - A[5] * A[7]; Ai[1] = A[2] * A[7] - A[1] * A[8]; Ai[2] = A[1] * A[5] - A[2] * A[4];
+    Ai[3] = A[5] * A[6] - A[3] * A[8]; Ai[4] = A[0] * A[8] - A[2] * A[6]; Ai[5] = A[2] * A[3] - A[0] * A[5];
+    Ai[6] = A[3] * A[7] - A[4] * A[6]; Ai[7] = A[1] * A[6] - A[0] * A[7]; Ai[8] = A[0] * A[4] - A[1] * A[3];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++)
+            BA[3 * r + c] = (B[3 * r] * Ai[c] + B[3 * r + 1] * Ai[3 + c] + B[3 * r + 2] * Ai[6 + c]) / det;
+    for (int r = 0; r < 3; r++) v[r] = BA[3 * r] * ta[0] + BA[3 * r + 1] * ta[1] + BA[3 * r + 2] * ta[2] - tb[r];
+    double s2 = 0.0;
+    for (int c = 0; c < 8; c++) {
+        const double y[3] = {c & 1 ? la.hi[0] : la.lo[0], c & 2 ? la.hi[1] : la.lo[1], c & 4 ? la.hi[2] : la.lo[2]};
+        double d2 = 0.0;
+        for (int r = 0; r < 3; r++) {
+            const double d = y[r] - (BA[3 * r] * y[0] + BA[3 * r + 1] * y[1] + BA[3 * r + 2] * y[2]) + v[r];
+            d2 += d * d;
+        }
+        s2 = fmax(s2, d2);
+    }
+    const float step = launch > 0 ? (float)sqrt(s2) : 0.f, prev = pose[kPoseStep];
+    float beta = 0.f;
+    const float ratio = launch == 1 ? kLookR1 : (prev > 0.f ? step / prev : 0.f);
+    if (!la.off && launch > 0 && step > 0.f && ratio > 0.f && ratio < 1.f) {  // (false for a NaN)
+        const float r = fminf(ratio, kLookRmax);
+        beta = la.alpha * r / (1.f - r);
+        if (beta * step > la.cap) beta = la.cap / step;
+    }
+    pose[kPoseStep] = step;
+    pose[kPoseBeta] = beta;
+    pose[kPoseOff] = beta * step;
+    // T_c: beta = 0 gives the pose itself, bit for bit
+    for (int k = 0; k < 12; k++) pose[kPoseC + k] = __fmaf_rn(beta, pose[k] - pose[12 + k], pose[k]);
+    for (int k = 0; k < 12; k++) hist[k] = pose[kPoseC + k];
 }
 
 __host__ __device__ int icp_solve(const double acc[24], int do_scale, double dT[16]);
@@ -1860,7 +2097,15 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
             hp.t[r] = (float)T[4 * r + 3];
         }
     }
-    hipLaunchKernelGGL(k_pose_set, dim3(1), dim3(1), 0, ctx->stream, T_dev, hp, icp->pose_dev,
+    LookAhead la{};
+    for (int k = 0; k < 3; k++) {
+        la.lo[k] = (float)(a.g.o[k] - rmax);
+        la.hi[k] = (float)(a.g.o[k] + a.g.n[k] * a.g.h + rmax);
+    }
+    la.alpha = kLookAlpha;
+    la.cap = kLookCap;
+    la.off = icp->no_look ? 1 : 0;
+    hipLaunchKernelGGL(k_pose_set, dim3(1), dim3(1), 0, ctx->stream, T_dev, hp, la, icp->pose_dev,
                        icp->pose_hist + (icp->launches & (icp->narrow ? 63 : kHist - 1)) * 12,
                        (uint32_t)icp->launches);
     a.pose = icp->pose_dev;  // every kernel reads the pose (and the previous one) from HBM
@@ -1917,13 +2162,24 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     PCP_HIP(ctx, hipEventRecord(e0, ctx->stream));
     const bool verify = a.g.dense && icp->launches > 0;  // the first launch has nothing cached
     icp->last_verified = verify;
+    // the search lists: the look-ahead form unless it is switched off (beta = 0: T_c = T_t).  Launch
+    // 1 has no step ratio yet, so beta = 0 there too, and the plain form is the faster one on its
+    // long list (measured 1.57 against 1.88 ms on the C4 registration).  A captured graph is
+    // replayed at every later launch, so it holds the look-ahead form and starts at launch 2:
+    // replayed and plain launches then run the same kernels at every launch.
+    using OctKernel = void (*)(IcpArgs, const int32_t*, const uint32_t*);
+    const OctKernel oct_graph =
+        icp->no_look ? k_icp_octant<PCP_OCT_WAVES_LIST, false> : k_icp_octant<PCP_OCT_WAVES_LIST, true>;
+    const OctKernel oct_list =
+        kLookR1 == 0.f && icp->launches <= 1 ? k_icp_octant<PCP_OCT_WAVES_LIST, false> : oct_graph;
     // A device-pose launch after the first is the same five kernels every time (verify, list
     // concatenation, octant search, list concatenation, fallback) with the same arguments: the
     // launch index is read from the device (k_pose_set) and the pose was already.  With
     // PCP_ICP_OPT_GRAPH the section is captured once per handle into a HIP graph and replayed --
     // one launch instead of five (measured: host enqueue is not what the loop waits for, and the
     // replayed section ran 0.5 % slower, so it is off by default).
-    if (icp->graph && T_dev && verify && !icp->dbg && !corr_idx && !args_out && !icp->graph_off) {
+    if (icp->graph && T_dev && verify && !icp->dbg && !corr_idx && !args_out && !icp->graph_off &&
+        oct_list == oct_graph) {
         a.oct_g = icp->oct_g_list;
         a.ring_g = icp->ring_g;
         auto section = [&](hipStream_t st) {
@@ -1934,8 +2190,8 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
                                (const int32_t*)icp->sv, (const uint32_t*)icp->sv_count, b.nseg_v, b.sv_seg, icp->svc,
                                icp->sv_off + b.nseg_v);
             b.partials = part_o;
-            hipLaunchKernelGGL(k_icp_octant<PCP_OCT_WAVES_LIST>, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, st, b,
-                               (const int32_t*)icp->svc, (const uint32_t*)(icp->sv_off + b.nseg_v));
+            hipLaunchKernelGGL(oct_graph, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, st, b, (const int32_t*)icp->svc,
+                               (const uint32_t*)(icp->sv_off + b.nseg_v));
             hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((b.nseg + 3) / 4)), dim3(256), 0, st,
                                (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, b.nseg, b.fb_seg, icp->fbc,
                                icp->fb_off + b.nseg);
@@ -1994,11 +2250,10 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
             const uint32_t* lst_n = verify ? (const uint32_t*)(icp->sv_off + a.nseg_v) : nullptr;
             a.oct_g = verify ? icp->oct_g_list : icp->oct_g_first;
             if (verify)
-                hipLaunchKernelGGL(k_icp_octant<PCP_OCT_WAVES_LIST>, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0,
+                hipLaunchKernelGGL(oct_list, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, ctx->stream, a, lst, lst_n);
+            else  // every query, beta = 0: the plain form
+                hipLaunchKernelGGL((k_icp_octant<PCP_OCT_WAVES, false>), dim3(icp->nb_fast), dim3(kIcpBlock), 0,
                                    ctx->stream, a, lst, lst_n);
-            else
-                hipLaunchKernelGGL(k_icp_octant<PCP_OCT_WAVES>, dim3(icp->nb_fast), dim3(kIcpBlock), 0, ctx->stream,
-                                   a, lst, lst_n);
         }
     } else {
         PCP_HIP(ctx, hipMemsetAsync(part_v, 0, (size_t)(icp->nb_ver + icp->nb_fast) * kAcc * sizeof(double),
@@ -2203,7 +2458,8 @@ int icp_make(pcp_ctx* ctx, const pcp_index* target, QXyz* q3, int32_t* qi, int64
     icp->nseg_v = nwaves_v;
     int rc = dmalloc(ctx, &icp->partials, (size_t)(icp->nb_ver + icp->nb_fast + icp->nb_ring) * kAcc);
     if (!rc) rc = dmalloc(ctx, &icp->acc, kAcc);
-    if (!rc) rc = dmalloc(ctx, &icp->pose_dev, 32);  // 24 pose floats + the launch index
+    // 24 pose floats, the launch index, the look-ahead state and map (kPoseStep .. kPoseWords)
+    if (!rc) rc = dmalloc(ctx, &icp->pose_dev, kPoseWords);
     // 12-byte cache records when every position (and the far sentinel) fits 26 bits
     icp->narrow = target->n + 1 < (int64_t)kPos26;
     const int rw = icp->narrow ? 3 : 4;  // words per record
@@ -2222,7 +2478,7 @@ int icp_make(pcp_ctx* ctx, const pcp_index* target, QXyz* q3, int32_t* qi, int64
                          : hipMemsetAsync(icp->cand + r0 * rw, 0xff, (size_t)nr * 16, ctx->stream);
     if (!rc && (me != hipSuccess ||
                 hipMemsetAsync(icp->pose_hist, 0, kHist * 12 * sizeof(float), ctx->stream) != hipSuccess ||
-                hipMemsetAsync(icp->pose_dev, 0, 32 * sizeof(float), ctx->stream) != hipSuccess))
+                hipMemsetAsync(icp->pose_dev, 0, kPoseWords * sizeof(float), ctx->stream) != hipSuccess))
         rc = set_error(ctx, PCP_ERR_HIP, "memset");
     if (!rc) rc = dmalloc(ctx, &icp->sv, (size_t)icp->nseg_v * icp->sv_seg + 1);
     if (!rc) rc = dmalloc(ctx, &icp->sv_count, (size_t)icp->nseg_v);
@@ -2345,8 +2601,9 @@ int pcp_icp_set_options(pcp_icp* icp, int oct_lanes_first, int oct_lanes_list, i
     icp->oct_g_first = oct_lanes_first ? oct_lanes_first : 1;
     icp->oct_g_list = oct_lanes_list;
     icp->ring_g = ring_lanes;
-    icp->dbg = ablate & ~(PCP_ICP_OPT_WIDE_CACHE | PCP_ICP_OPT_GRAPH);
+    icp->dbg = ablate & ~(PCP_ICP_OPT_WIDE_CACHE | PCP_ICP_OPT_GRAPH | PCP_ICP_OPT_NO_LOOKAHEAD);
     icp->graph = (ablate & PCP_ICP_OPT_GRAPH) != 0;
+    icp->no_look = (ablate & PCP_ICP_OPT_NO_LOOKAHEAD) != 0;
     return PCP_OK;
 }
 
@@ -2630,6 +2887,18 @@ int pcp_icp_last_fallback(const pcp_icp* icp, int64_t* n) {
 int pcp_icp_last_searched(const pcp_icp* icp, int64_t* n) {
     if (!icp || !n) return PCP_ERR_ARG;
     *n = icp->last_searched;
+    return PCP_OK;
+}
+
+int pcp_icp_last_lookahead(const pcp_icp* icp, double* beta, double* max_offset_m) {
+    if (!icp || !icp->ctx) return PCP_ERR_ARG;
+    pcp_ctx* ctx = icp->ctx;
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    float w[2] = {0.f, 0.f};
+    PCP_HIP(ctx, hipMemcpyAsync(w, icp->pose_dev + pcp::kPoseBeta, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (beta) *beta = w[0];
+    if (max_offset_m) *max_offset_m = w[1];
     return PCP_OK;
 }
 

@@ -350,15 +350,18 @@ class ICP:
 
     WIDE_CACHE = 128  # PCP_ICP_OPT_WIDE_CACHE
     GRAPH = 256       # PCP_ICP_OPT_GRAPH
+    NO_LOOKAHEAD = 512  # PCP_ICP_OPT_NO_LOOKAHEAD
 
     def set_options(self, oct_lanes_first=1, oct_lanes_list=0, ring_lanes=0, ablate=0, wide_cache=False,
-                    graph=False):
+                    graph=False, lookahead=True):
         """Test / profiling controls (pcp_icp_set_options): lanes per query of the octant pass
         (first launch, later lists; 0 = by density) and of the fallback pass (0 = by length);
         `ablate` switches passes off (results are then wrong); `wide_cache` keeps 16-byte cache
         records (before the first step); `graph` replays one captured HIP graph per device-pose
-        launch (results are identical in both cases)."""
-        flags = int(ablate) | (self.WIDE_CACHE if wide_cache else 0) | (self.GRAPH if graph else 0)
+        launch; `lookahead=False` searches around the query itself instead of ahead on its path
+        (results are identical in all three cases)."""
+        flags = (int(ablate) | (self.WIDE_CACHE if wide_cache else 0) | (self.GRAPH if graph else 0) |
+                 (0 if lookahead else self.NO_LOOKAHEAD))
         self.ctx.check(self.ctx.lib.pcp_icp_set_options(self.h, int(oct_lanes_first), int(oct_lanes_list),
                                                         int(ring_lanes), flags))
 
@@ -445,6 +448,12 @@ class ICP:
         n = C.c_int64()
         self.ctx.check(self.ctx.lib.pcp_icp_last_searched(self.h, C.byref(n)))
         return n.value
+
+    def last_lookahead(self):
+        """(beta, largest offset in metres) of the last launch's look-ahead search centre."""
+        b, m = C.c_double(), C.c_double()
+        self.ctx.check(self.ctx.lib.pcp_icp_last_lookahead(self.h, C.byref(b), C.byref(m)))
+        return b.value, m.value
 
     def last_fallback(self):
         n = C.c_int64()
