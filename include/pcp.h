@@ -73,6 +73,12 @@ int         pcp_ctx_set_stream(pcp_ctx* ctx, void* stream);
 void*       pcp_ctx_stream(pcp_ctx* ctx);
 const char* pcp_last_error(const pcp_ctx* ctx);
 int         pcp_sync(pcp_ctx* ctx);
+/* Diagnostics: the context's internal device allocator (index builds, ICP state, per-call
+ * temporaries; not pcp_malloc).  out[0] = blocks currently handed out, out[1] = their bytes,
+ * out[2] = the peak of out[1] since pcp_ctx_create, out[3] = hipMalloc calls made so far.  A call
+ * that returns, with or without an error, leaves out[0] where it was plus what the handles it
+ * created own.  No reference counterpart. */
+int         pcp_ctx_alloc_stats(const pcp_ctx* ctx, int64_t out[4]);
 /* Diagnostics: on SIGSEGV/SIGBUS/SIGILL/SIGFPE/SIGABRT print the faulting library (dladdr) and
  * native frames to stderr, then chain to the previously installed handler (no reference
  * counterpart; the reference process has no fault reporting). */

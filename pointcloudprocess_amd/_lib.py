@@ -30,6 +30,7 @@ SIGNATURES = [
     ("pcp_ctx_stream", _vp, [_vp]),
     ("pcp_last_error", C.c_char_p, [_vp]),
     ("pcp_sync", _i32, [_vp]),
+    ("pcp_ctx_alloc_stats", _i32, [_vp, _vp]),
     ("pcp_malloc", _i32, [_vp, _P(_vp), _sz]),
     ("pcp_free", _i32, [_vp, _vp]),
     ("pcp_memcpy_h2d", _i32, [_vp, _vp, _vp, _sz]),

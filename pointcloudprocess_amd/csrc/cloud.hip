@@ -14,9 +14,8 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.hpp"
+#include "sortcfg.hpp"
 
 namespace pcp {
 namespace {
@@ -211,35 +210,19 @@ __global__ __launch_bounds__(kB) void k_centre_f32(const P48* in, int64_t n, dou
     }
 }
 
-// device buffers of one voxel-filter call
-struct VoxBufs {
-    pcp_ctx* ctx;
-    uint32_t* flag = nullptr;
-    uint32_t* k0 = nullptr;
-    uint32_t* k1 = nullptr;
-    uint32_t* v0 = nullptr;
-    uint32_t* v1 = nullptr;
-    uint32_t* head = nullptr;
-    void* tmp = nullptr;
-    ~VoxBufs() {
-        dfree(ctx, flag); dfree(ctx, k0); dfree(ctx, k1); dfree(ctx, v0); dfree(ctx, v1); dfree(ctx, head);
-        dfree(ctx, tmp);
-    }
-};
-
 }  // namespace
 
 int minmax_aos48_dev(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, double mn[4], double mx[4]) {
     for (int a = 0; a < 4; a++) { mn[a] = DBL_MAX; mx[a] = DBL_MIN; }
     if (n <= 0) return PCP_OK;
     const unsigned nb = grid_for(n, kB, kRedBlocks);
+    Tmp tmp(ctx);
     double* part;
-    PCP_TRY(dmalloc(ctx, &part, 8 * (size_t)nb));
+    PCP_TRY(tmp.get(&part, 8 * (size_t)nb));
     hipLaunchKernelGGL(k_minmax48, dim3(nb), dim3(kB), 0, ctx->stream, (const P48*)in, n, is_dense, part);
     std::vector<double> h(8 * nb);
     hipError_t e = hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dfree(ctx, part);
     if (e != hipSuccess) return hip_fail(ctx, e, "minmax", __FILE__, __LINE__);
     for (unsigned b = 0; b < nb; b++)
         for (int a = 0; a < 4; a++) {
@@ -292,35 +275,33 @@ static int voxel_filter_impl(pcp_ctx* ctx, const P48* in, int64_t n, int is_dens
     g.mul1 = (uint32_t)div_b[0];  // divb_mul_ in wrapping int32 (:847)
     g.mul2 = (uint32_t)div_b[0] * (uint32_t)div_b[1];
 
-    VoxBufs b{ctx};
-    PCP_TRY(dmalloc(ctx, &b.k0, n));
-    PCP_TRY(dmalloc(ctx, &b.k1, n));
-    PCP_TRY(dmalloc(ctx, &b.v0, n));
-    PCP_TRY(dmalloc(ctx, &b.v1, n));
-    PCP_TRY(dmalloc(ctx, &b.head, n + 1));
+    Tmp tmp(ctx);
+    uint32_t *k0, *k1, *v0, *v1, *head, *flag = nullptr;
+    PCP_TRY(tmp.get(&k0, n));
+    PCP_TRY(tmp.get(&k1, n));
+    PCP_TRY(tmp.get(&v0, n));
+    PCP_TRY(tmp.get(&v1, n));
+    PCP_TRY(tmp.get(&head, n + 1));
     int64_t m = n;
     if (!is_dense) {
-        PCP_TRY(dmalloc(ctx, &b.flag, n + 1));
-        hipLaunchKernelGGL(k_vox_flag, dim3(grid_for(n, kB)), dim3(kB), 0, st, in, n, is_dense, b.flag);
+        PCP_TRY(tmp.get(&flag, n + 1));
+        hipLaunchKernelGGL(k_vox_flag, dim3(grid_for(n, kB)), dim3(kB), 0, st, in, n, is_dense, flag);
         uint32_t valid = 0;
-        PCP_TRY(scan_u32_inplace(ctx, b.flag, n, &valid));
+        PCP_TRY(scan_u32_inplace(ctx, flag, n, &valid));
         m = valid;
     }
-    hipLaunchKernelGGL(k_vox_key, dim3(grid_for(n, kB)), dim3(kB), 0, st, in, n, is_dense, g, b.flag, b.k0, b.v0);
+    hipLaunchKernelGGL(k_vox_key, dim3(grid_for(n, kB)), dim3(kB), 0, st, in, n, is_dense, g, flag, k0, v0);
     PCP_LAUNCH_CHECK(ctx);
     if (m == 0) return PCP_OK;
     // stable LSD radix sort by the u32 key (voxel_grid.h:948)
-    size_t tmp_bytes = 0;
-    PCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, b.k0, b.k1, b.v0, b.v1, (size_t)m, 0, 32, st));
-    PCP_TRY(dmalloc(ctx, (char**)&b.tmp, tmp_bytes));
-    PCP_HIP(ctx, rocprim::radix_sort_pairs(b.tmp, tmp_bytes, b.k0, b.k1, b.v0, b.v1, (size_t)m, 0, 32, st));
+    PCP_TRY(sort_pairs(tmp, k0, k1, v0, v1, (size_t)m, 0, 32));
     // runs of equal keys = voxels (:952-960)
-    hipLaunchKernelGGL(k_run_heads, dim3(grid_for(m, kB)), dim3(kB), 0, st, b.k1, m, b.head);
+    hipLaunchKernelGGL(k_run_heads, dim3(grid_for(m, kB)), dim3(kB), 0, st, k1, m, head);
     uint32_t nvox = 0;
-    PCP_TRY(scan_u32_inplace(ctx, b.head, m, &nvox));
-    uint32_t* start = b.k0;  // reuse
-    hipLaunchKernelGGL(k_run_starts, dim3(grid_for(m, kB)), dim3(kB), 0, st, b.k1, b.head, m, start);
-    hipLaunchKernelGGL(k_vox_reduce, dim3(grid_for(nvox, kB)), dim3(kB), 0, st, in, b.k1, b.v1, start,
+    PCP_TRY(scan_u32_inplace(ctx, head, m, &nvox));
+    uint32_t* start = k0;  // reuse
+    hipLaunchKernelGGL(k_run_starts, dim3(grid_for(m, kB)), dim3(kB), 0, st, k1, head, m, start);
+    hipLaunchKernelGGL(k_vox_reduce, dim3(grid_for(nvox, kB)), dim3(kB), 0, st, in, k1, v1, start,
                        (int64_t)nvox, m, all_data, out, out_vidx);
     PCP_LAUNCH_CHECK(ctx);
     PCP_HIP(ctx, hipStreamSynchronize(st));
@@ -393,14 +374,15 @@ int pcp_remove_duplicate(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, 
     double c[4] = {0, 0, 0, 0};
     PCP_TRY(centroid_aos48_dev(ctx, in, n, is_dense, c, nullptr));  // :45
     double T[16] = {1, 0, 0, -c[0], 0, 1, 0, -c[1], 0, 0, 1, -c[2], 0, 0, 0, 1};
-    P48* tmp = nullptr;
-    PCP_TRY(dmalloc(ctx, &tmp, n));
-    hipLaunchKernelGGL(k_copy_centre, dim3(grid_for(n, kB)), dim3(kB), 0, ctx->stream, (const P48*)in, tmp, n, is_dense,
+    Tmp tmp(ctx);
+    P48* cen = nullptr;  // the centred copy
+    PCP_TRY(tmp.get(&cen, n));
+    hipLaunchKernelGGL(k_copy_centre, dim3(grid_for(n, kB)), dim3(kB), 0, ctx->stream, (const P48*)in, cen, n, is_dense,
                        make_xf(T));
     const double lf = (double)leaf;  // float leaf widened (:57)
     const double l3[3] = {lf, lf, lf};
     int64_t m = 0;
-    int rc = voxel_filter_impl(ctx, tmp, n, is_dense, l3, 1, (P48*)out, &m, nullptr);
+    int rc = voxel_filter_impl(ctx, cen, n, is_dense, l3, 1, (P48*)out, &m, nullptr);
     if (rc == PCP_OK && m > 0) {
         T[3] = c[0]; T[7] = c[1]; T[11] = c[2];  // :60-61
         hipLaunchKernelGGL(k_transform48, dim3(grid_for(m, kB)), dim3(kB), 0, ctx->stream, (const P48*)out, (P48*)out,
@@ -409,7 +391,6 @@ int pcp_remove_duplicate(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, 
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = hip_fail(ctx, e, "remove_duplicate", __FILE__, __LINE__);
     }
-    dfree(ctx, tmp);
     if (rc == PCP_OK) *n_out = m;
     return rc;
 }
@@ -438,8 +419,9 @@ int pcp_get_rot_icp(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, co
     const double c[3] = {s[0] / dn, s[1] / dn, s[2] / dn};
     float* fs = nullptr;
     float* ft = nullptr;
-    PCP_TRY(dmalloc(ctx, &fs, 3 * (size_t)ns));
-    int rc = dmalloc(ctx, &ft, 3 * (size_t)nt);
+    Tmp bufs(ctx);
+    PCP_TRY(bufs.get(&fs, 3 * (size_t)ns));
+    int rc = bufs.get(&ft, 3 * (size_t)nt);
     pcp_index* ix = nullptr;
     pcp_icp* icp = nullptr;
     if (rc == PCP_OK) {
@@ -468,8 +450,6 @@ int pcp_get_rot_icp(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, co
     }
     if (icp) pcp_icp_destroy(icp);
     if (ix) pcp_index_destroy(ix);
-    dfree(ctx, fs);
-    dfree(ctx, ft);
     return rc;
 }
 

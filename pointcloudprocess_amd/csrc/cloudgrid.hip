@@ -22,9 +22,7 @@
 #include <cmath>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "common.hpp"
+#include "sortcfg.hpp"
 
 struct pcp_grid {
     pcp_ctx* ctx = nullptr;
@@ -284,26 +282,6 @@ __global__ void k_grid_gather_sorted(const uint8_t* pts, const uint64_t* skeys, 
     }
 }
 
-struct Tmp {  // per-call device temporaries, returned to the context's cache on scope exit
-    pcp_ctx* ctx;
-    std::vector<void*> v;
-    explicit Tmp(pcp_ctx* c) : ctx(c) {}
-    ~Tmp() {
-        for (void* p : v) dfree(ctx, p);
-    }
-    template <typename T>
-    int get(T** p, size_t n) {
-        PCP_TRY(dmalloc(ctx, p, n));
-        v.push_back((void*)*p);
-        return PCP_OK;
-    }
-    // hand an allocation over to the caller (on success): the guard no longer frees it
-    void release(const void* p) {
-        for (void*& q : v)
-            if (q == p) q = nullptr;
-    }
-};
-
 }  // namespace
 }  // namespace pcp
 
@@ -372,11 +350,7 @@ int pcp_grid_add_cloud(pcp_ctx* ctx, pcp_grid* g, const void* cloud_dev, int64_t
     PCP_TRY(tmp.get(&rec, 48 * m));
     hipLaunchKernelGGL(k_grid_keys, dim3(grid_for(m, 256)), dim3(256), 0, st, g->pts, g->n, (const uint8_t*)cloud_dev,
                        n, k0, o0);
-    size_t tb = 0;
-    PCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, k0, k1, o0, o1, (size_t)m, 0, 64, st));
-    void* sortmem;
-    PCP_TRY(tmp.get((char**)&sortmem, tb));
-    PCP_HIP(ctx, rocprim::radix_sort_pairs(sortmem, tb, k0, k1, o0, o1, (size_t)m, 0, 64, st));
+    PCP_TRY(sort_pairs(tmp, k0, k1, o0, o1, (size_t)m, 0, 64));
     hipLaunchKernelGGL(k_grid_gather, dim3(grid_for(m, 256)), dim3(256), 0, st, g->pts, g->n,
                        (const uint8_t*)cloud_dev, o1, m, rec);
     hipLaunchKernelGGL(k_grid_heads, dim3(grid_for(m, 256)), dim3(256), 0, st, k1, m, head);
@@ -499,11 +473,7 @@ int pcp_grid_match(pcp_ctx* ctx, const pcp_grid* g, const void* src_dev, int64_t
     PCP_TRY(tmp.get(&dk, nd));
     PCP_TRY(tmp.get(&dk1, nd));
     hipLaunchKernelGGL(k_grid_dst_keys, dim3(grid_for(g->n, 256)), dim3(256), 0, st, first, g->n, pos, dk);
-    size_t tb = 0;
-    PCP_HIP(ctx, rocprim::radix_sort_keys(nullptr, tb, dk, dk1, (size_t)nd, 0, 64, st));
-    void* sortmem;
-    PCP_TRY(tmp.get((char**)&sortmem, tb));
-    PCP_HIP(ctx, rocprim::radix_sort_keys(sortmem, tb, dk, dk1, (size_t)nd, 0, 64, st));
+    PCP_TRY(sort_keys(tmp, dk, dk1, (size_t)nd, 0, 64));
     hipLaunchKernelGGL(k_grid_gather_sorted, dim3(grid_for(nd, 256)), dim3(256), 0, st, g->pts, dk1, (int64_t)nd,
                        (uint8_t*)dst_dev);
     PCP_LAUNCH_CHECK(ctx);

@@ -45,6 +45,9 @@ struct pcp_ctx {
     std::multimap<size_t, void*> free_blocks;
     std::unordered_map<void*, size_t> block_size;
     size_t cached_bytes = 0;
+    // pcp_ctx_alloc_stats: bytes handed out now, their peak, hipMalloc calls of cache_alloc
+    size_t out_bytes = 0, peak_bytes = 0;
+    int64_t n_hipmalloc = 0;
     size_t cache_cap = (size_t)16 << 30;  // set from the device size at create (a third of HBM)
     // lifetime: every index / ICP handle / CloudGrid made on the context holds a reference, so
     // the objects may be destroyed before OR after pcp_ctx_destroy (a garbage-collected host
@@ -95,6 +98,43 @@ int dmalloc(pcp_ctx* ctx, T** p, size_t count) {
     *p = (T*)v;
     return rc;
 }
+
+// Device temporaries of one call.  get() takes a block from ctx's cache and the destructor gives
+// back whatever is still held, so no return path leaks.  The cache serves later requests of the
+// same call from freed blocks: a temporary that is dead before a later allocation is returned
+// there with free(), not left to scope exit, or the call's peak footprint grows.
+struct Tmp {
+    pcp_ctx* ctx;
+    std::vector<void*> held;
+    explicit Tmp(pcp_ctx* c) : ctx(c) {}
+    Tmp(const Tmp&) = delete;
+    Tmp& operator=(const Tmp&) = delete;
+    ~Tmp() { free_all(); }
+    template <typename T>
+    int get(T** p, size_t count) {
+        PCP_TRY(dmalloc(ctx, p, count));
+        held.push_back((void*)*p);
+        return PCP_OK;
+    }
+    // hand a block over to a longer-lived owner: the guard no longer frees it
+    template <typename T>
+    T* release(T* p) {
+        for (void*& q : held)
+            if (q == (void*)p) q = nullptr;
+        return p;
+    }
+    // early free: the block goes back to the cache now and p is cleared
+    template <typename T>
+    void free(T*& p) {
+        dfree(ctx, release(p));
+        p = nullptr;
+    }
+    void free_all() {
+        for (void* p : held) dfree(ctx, p);
+        held.clear();
+    }
+};
+
 inline unsigned grid_for(int64_t n, int block, int64_t cap = 1 << 20) {
     int64_t g = (n + block - 1) / block;
     if (g < 1) g = 1;

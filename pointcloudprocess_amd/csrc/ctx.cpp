@@ -57,6 +57,11 @@ static size_t round_block(size_t b) {
     return (b + g - 1) / g * g;
 }
 
+static void handed_out(pcp_ctx* ctx, size_t bytes) {
+    ctx->out_bytes += bytes;
+    if (ctx->out_bytes > ctx->peak_bytes) ctx->peak_bytes = ctx->out_bytes;
+}
+
 int cache_alloc(pcp_ctx* ctx, size_t bytes, void** p) {
     *p = nullptr;
     const size_t want = round_block(bytes ? bytes : 1);
@@ -64,13 +69,16 @@ int cache_alloc(pcp_ctx* ctx, size_t bytes, void** p) {
     if (it != ctx->free_blocks.end() && it->first <= want + want / 4 + ((size_t)2 << 20)) {
         *p = it->second;
         ctx->cached_bytes -= it->first;
+        handed_out(ctx, it->first);
         ctx->free_blocks.erase(it);
         return PCP_OK;
     }
+    ctx->n_hipmalloc++;
     hipError_t e = hipMalloc(p, want);
     if (e != hipSuccess && !ctx->free_blocks.empty()) {  // give the cache back and retry
         (void)hipGetLastError();
         cache_release(ctx);
+        ctx->n_hipmalloc++;
         e = hipMalloc(p, want);
     }
     if (e != hipSuccess) {
@@ -79,6 +87,7 @@ int cache_alloc(pcp_ctx* ctx, size_t bytes, void** p) {
         return set_error(ctx, PCP_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
     }
     ctx->block_size[*p] = want;
+    handed_out(ctx, want);
     return PCP_OK;
 }
 
@@ -89,6 +98,7 @@ void dfree(pcp_ctx* ctx, void* p) {
         (void)hipFree(p);
         return;
     }
+    ctx->out_bytes -= it->second;
     if (ctx->closing) {  // nothing is cached on a closing context
         ctx->block_size.erase(it);
         (void)hipFree(p);
@@ -216,6 +226,15 @@ int pcp_ctx_set_stream(pcp_ctx* ctx, void* stream) {
 void* pcp_ctx_stream(pcp_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
 const char* pcp_last_error(const pcp_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null ctx"; }
+
+int pcp_ctx_alloc_stats(const pcp_ctx* ctx, int64_t out[4]) {
+    if (!ctx || !out) return PCP_ERR_ARG;
+    out[0] = (int64_t)ctx->block_size.size() - (int64_t)ctx->free_blocks.size();
+    out[1] = (int64_t)ctx->out_bytes;
+    out[2] = (int64_t)ctx->peak_bytes;
+    out[3] = ctx->n_hipmalloc;
+    return PCP_OK;
+}
 
 int pcp_sync(pcp_ctx* ctx) {
     if (!ctx) return PCP_ERR_ARG;

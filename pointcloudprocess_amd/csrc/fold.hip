@@ -297,27 +297,21 @@ int seqfold_aos48(pcp_ctx* ctx, const void* p0, int64_t n0, const void* p1, int6
     double4 *sums = nullptr, *est = nullptr;
     FoldMap* maps = nullptr;
     double* out = nullptr;
-    int rc = dmalloc(ctx, &sums, nchunks);
-    if (!rc) rc = dmalloc(ctx, &est, nchunks);
-    if (!rc) rc = dmalloc(ctx, &maps, 3 * nchunks);
-    if (!rc) rc = dmalloc(ctx, &out, 4);
-    if (!rc) {
-        hipStream_t st = ctx->stream;
-        const unsigned nb = (unsigned)((nchunks + 3) / 4);
-        hipLaunchKernelGGL(k_fold_sums, dim3(nb), dim3(256), 0, st, src, nchunks, sums);
-        hipLaunchKernelGGL(k_fold_prefix, dim3(1), dim3(kPfxThreads), 0, st, sums, nchunks, est);
-        hipLaunchKernelGGL(k_fold_maps, dim3(nb), dim3(256), 0, st, src, nchunks, est, maps);
-        hipLaunchKernelGGL(k_fold_scan, dim3(1), dim3(64), 0, st, src, nchunks, maps, sums, out);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(s_host, out, 4 * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = hip_fail(ctx, e, "sequential fold", __FILE__, __LINE__);
-    }
-    dfree(ctx, sums);
-    dfree(ctx, est);
-    dfree(ctx, maps);
-    dfree(ctx, out);
-    return rc;
+    Tmp tmp(ctx);
+    PCP_TRY(tmp.get(&sums, nchunks));
+    PCP_TRY(tmp.get(&est, nchunks));
+    PCP_TRY(tmp.get(&maps, 3 * nchunks));
+    PCP_TRY(tmp.get(&out, 4));
+    hipStream_t st = ctx->stream;
+    const unsigned nb = (unsigned)((nchunks + 3) / 4);
+    hipLaunchKernelGGL(k_fold_sums, dim3(nb), dim3(256), 0, st, src, nchunks, sums);
+    hipLaunchKernelGGL(k_fold_prefix, dim3(1), dim3(kPfxThreads), 0, st, sums, nchunks, est);
+    hipLaunchKernelGGL(k_fold_maps, dim3(nb), dim3(256), 0, st, src, nchunks, est, maps);
+    hipLaunchKernelGGL(k_fold_scan, dim3(1), dim3(64), 0, st, src, nchunks, maps, sums, out);
+    PCP_LAUNCH_CHECK(ctx);
+    PCP_HIP(ctx, hipMemcpyAsync(s_host, out, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    PCP_HIP(ctx, hipStreamSynchronize(st));
+    return PCP_OK;
 }
 
 }  // namespace pcp

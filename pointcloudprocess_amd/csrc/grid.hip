@@ -9,7 +9,6 @@
 #include <cmath>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include "sortcfg.hpp"
 
 #include "grid.hpp"
@@ -402,9 +401,13 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
     ix->owner = ctx;
     ctx_retain(ctx);
     ix->n_in = n_in;
-    auto fail = [&](int rc) { pcp_index_destroy(ix); return rc; };
+    // every return but the last destroys the half-built index (and drops its context reference)
+    struct Unbuilt {
+        pcp_index* ix;
+        ~Unbuilt() { if (ix) pcp_index_destroy(ix); }
+    } unbuilt{ix};
+    Tmp tmp(ctx);
 
-    int rc;
     T* cxyz = nullptr;
     double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
     // ---- bbox + non-finite count in one pass; an all-finite cloud without an indices subset is
@@ -415,20 +418,17 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
         const unsigned nbk = grid_for(n_in, kB, kBboxBlocks);
         double* part = nullptr;
         unsigned long long* d_bad = nullptr;
-        if ((rc = dmalloc(ctx, &part, 6 * (size_t)nbk)) || (rc = dmalloc(ctx, &d_bad, 1))) {
-            dfree(ctx, part);
-            return fail(rc);
-        }
-        hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), st);
+        PCP_TRY(tmp.get(&part, 6 * (size_t)nbk));
+        PCP_TRY(tmp.get(&d_bad, 1));
+        PCP_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(k_bbox_count<T>, dim3(nbk), dim3(kB), 0, st, xyz, stride, n_in, part, d_bad);
         std::vector<double> hp(6 * nbk);
         unsigned long long bad = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        dfree(ctx, part);
-        dfree(ctx, d_bad);
-        if (e != hipSuccess) return fail(hip_fail(ctx, e, "bbox", __FILE__, __LINE__));
+        PCP_HIP(ctx, hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        PCP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
+        PCP_HIP(ctx, hipStreamSynchronize(st));
+        tmp.free(part);
+        tmp.free(d_bad);
         if (bad < (unsigned long long)n_in) {  // the bbox of the finite points = the compacted cloud's
             have_bbox = true;
             for (int a = 0; a < 3; a++) { mn[a] = INFINITY; mx[a] = -INFINITY; }
@@ -445,32 +445,27 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
         }
     }
     // ---- compaction (convertCloudToArray)
-    uint32_t* flag = nullptr;
-    uint32_t* bits = nullptr;
-    const int64_t nw = (n_in + 31) / 32;
     if (!direct) {
-        if ((rc = dmalloc(ctx, &flag, n_in + 1)) || (rc = dmalloc(ctx, &bits, nw + 1))) {
-            dfree(ctx, flag); dfree(ctx, bits);
-            return fail(rc);
-        }
+        uint32_t* flag = nullptr;
+        uint32_t* bits = nullptr;
+        const int64_t nw = (n_in + 31) / 32;
+        PCP_TRY(tmp.get(&flag, n_in + 1));
+        PCP_TRY(tmp.get(&bits, nw + 1));
         uint32_t nvalid = 0;
         if (n_in > 0) {
             hipLaunchKernelGGL(k_valid<T>, dim3(grid_for(n_in, kB)), dim3(kB), 0, st, xyz, stride, n_in, indices, flag);
             hipLaunchKernelGGL(k_pack_bits, dim3((unsigned)((n_in + kB - 1) / kB)), dim3(kB), 0, st, flag, n_in, bits);
-            rc = scan_u32_inplace(ctx, flag, n_in, &nvalid);
-            if (rc) { dfree(ctx, flag); dfree(ctx, bits); return fail(rc); }
+            PCP_TRY(scan_u32_inplace(ctx, flag, n_in, &nvalid));
         }
         ix->n = nvalid;
         ix->identity = (indices == nullptr && (int64_t)nvalid == n_in) ? 1 : 0;
-        if ((rc = dmalloc(ctx, &cxyz, 3 * (size_t)(nvalid + 1))) || (rc = dmalloc(ctx, &ix->mapping, nvalid + 1))) {
-            dfree(ctx, flag); dfree(ctx, bits); dfree(ctx, cxyz);
-            return fail(rc);
-        }
+        PCP_TRY(tmp.get(&cxyz, 3 * (size_t)(nvalid + 1)));
+        PCP_TRY(dmalloc(ctx, &ix->mapping, nvalid + 1));
         if (n_in > 0)
             hipLaunchKernelGGL(k_compact<T>, dim3(grid_for(n_in, kB)), dim3(kB), 0, st, xyz, stride, n_in,
                                indices, flag, bits, cxyz, ix->mapping);
-        dfree(ctx, flag);
-        dfree(ctx, bits);  // cached: reuse is stream-ordered on ctx's stream
+        tmp.free(flag);  // early: the cache serves the buffers below from these blocks
+        tmp.free(bits);  // (reuse is stream-ordered on ctx's stream)
     }
     const int64_t n = ix->n;
 
@@ -478,13 +473,12 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
     if (n > 0 && !have_bbox) {
         const unsigned nbk = grid_for(n, kB, kBboxBlocks);
         double* part;
-        if ((rc = dmalloc(ctx, &part, 6 * (size_t)nbk))) { dfree(ctx, cxyz); return fail(rc); }
+        PCP_TRY(tmp.get(&part, 6 * (size_t)nbk));
         hipLaunchKernelGGL(k_minmax<T>, dim3(nbk), dim3(kB), 0, st, cxyz, n, part);
         std::vector<double> hp(6 * nbk);
-        hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st);
-        hipError_t e = hipStreamSynchronize(st);
-        dfree(ctx, part);
-        if (e != hipSuccess) { dfree(ctx, cxyz); return fail(hip_fail(ctx, e, "bbox", __FILE__, __LINE__)); }
+        PCP_HIP(ctx, hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        PCP_HIP(ctx, hipStreamSynchronize(st));
+        tmp.free(part);
         for (int a = 0; a < 3; a++) { mn[a] = INFINITY; mx[a] = -INFINITY; }
         for (unsigned b = 0; b < nbk; b++)
             for (int a = 0; a < 3; a++) {
@@ -508,49 +502,39 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
         if (!(h > emax * 1e-7)) h = emax * 1e-7;
         if (!(h > 0)) h = 1.0;
     }
-    uint32_t* count = nullptr;
+    using V4 = typename Real<T>::V4;
     uint32_t* rank = nullptr;  // sort input values (point index)
     uint32_t* skey = nullptr;  // sort input keys (cell id)
-    if ((is_f64 && (rc = dmalloc(ctx, &rank, n + 1))) || (rc = dmalloc(ctx, &skey, n + 1))) {
-        dfree(ctx, rank);
-        dfree(ctx, cxyz);
-        return fail(rc);
-    }
-    if ((rc = dmalloc(ctx, (typename Real<T>::V4**)&ix->pts, n + 1))) {
-        dfree(ctx, rank); dfree(ctx, skey); dfree(ctx, cxyz);
-        return fail(rc);
-    }
+    if (is_f64) PCP_TRY(tmp.get(&rank, n + 1));
+    PCP_TRY(tmp.get(&skey, n + 1));
+    PCP_TRY(dmalloc(ctx, (V4**)&ix->pts, n + 1));
     bool hooked = false;
     for (int attempt = 0; attempt < 3; attempt++) {
         GridDesc g{};
         while (!make_geometry(g, mn, mx, h, cap)) h *= 2.0;
         dfree(ctx, ix->brick); ix->brick = nullptr;
-        dfree(ctx, count); count = nullptr;
         const int64_t ncells_dense = (int64_t)g.n[0] * g.n[1] * g.n[2];
         g.dense = (!force_sparse && ncells_dense <= dense_cap) ? 1 : 0;
         g.ncells = ncells_dense;
         int64_t ncells;
+        PCP_TRY(dmalloc(ctx, &ix->brick, g.nbricks));
+        PCP_HIP(ctx, hipMemsetAsync(ix->brick, 0, (size_t)g.nbricks * sizeof(int32_t), st));
         if (g.dense) {
             ncells = ncells_dense;
             g.nslots = 0;
-            if ((rc = dmalloc(ctx, &ix->brick, g.nbricks))) break;
-            PCP_HIP(ctx, hipMemsetAsync(ix->brick, 0, (size_t)g.nbricks * sizeof(int32_t), st));
             g.brick = ix->brick;  // marked by k_count, turned into 0 / -1 flags below
         } else {
-            if ((rc = dmalloc(ctx, &ix->brick, g.nbricks))) break;
-            PCP_HIP(ctx, hipMemsetAsync(ix->brick, 0, (size_t)g.nbricks * sizeof(int32_t), st));
             if (n > 0)  // the direct (uncompacted) fp32 path keys the caller's cloud in place
                 hipLaunchKernelGGL(k_mark<T>, dim3(grid_for(n, kB)), dim3(kB), 0, st, g, direct ? xyz : cxyz,
                                    direct ? stride / sizeof(T) : (size_t)3, n, ix->brick);
             const int64_t nbw = (g.nbricks + 31) / 32;
             uint32_t* bbits;
-            if ((rc = dmalloc(ctx, &bbits, nbw + 1))) break;
+            PCP_TRY(tmp.get(&bbits, nbw + 1));
             hipLaunchKernelGGL(k_brick_bits, dim3(grid_for(nbw, kB)), dim3(kB), 0, st, ix->brick, g.nbricks, bbits);
             uint32_t nslots = 0;
-            rc = scan_u32_inplace(ctx, (uint32_t*)ix->brick, g.nbricks, &nslots);
-            if (rc) { dfree(ctx, bbits); break; }
+            PCP_TRY(scan_u32_inplace(ctx, (uint32_t*)ix->brick, g.nbricks, &nslots));
             hipLaunchKernelGGL(k_brick_final, dim3(grid_for(g.nbricks, kB)), dim3(kB), 0, st, ix->brick, g.nbricks, bbits);
-            dfree(ctx, bbits);
+            tmp.free(bbits);
             g.nslots = nslots;
             g.brick = ix->brick;
             ncells = (int64_t)nslots * 64;
@@ -561,54 +545,51 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
             const int64_t nv = (ncells + 15) / 16;  // 16-byte vectors of cell flags
             uint4* cflag = nullptr;
             unsigned long long* d_ne = nullptr;
-            if ((rc = dmalloc(ctx, &cflag, nv)) || (rc = dmalloc(ctx, &d_ne, 1))) { dfree(ctx, cflag); break; }
-            hipError_t e = hipMemsetAsync(cflag, 0, (size_t)nv * sizeof(uint4), st);
-            if (e == hipSuccess) e = hipMemsetAsync(d_ne, 0, sizeof(unsigned long long), st);
+            PCP_TRY(tmp.get(&cflag, nv));
+            PCP_TRY(tmp.get(&d_ne, 1));
+            PCP_HIP(ctx, hipMemsetAsync(cflag, 0, (size_t)nv * sizeof(uint4), st));
+            PCP_HIP(ctx, hipMemsetAsync(d_ne, 0, sizeof(unsigned long long), st));
             hipLaunchKernelGGL(k_cell_flags<T>, dim3(grid_for(n, kB)), dim3(kB), 0, st, g, direct ? xyz : cxyz,
                                direct ? stride / sizeof(T) : (size_t)3, n, (uint8_t*)cflag);
             hipLaunchKernelGGL(k_count_flags, dim3(grid_for(nv, kB, 1024)), dim3(kB), 0, st, cflag, nv, d_ne);
             unsigned long long ne = 0;
-            if (e == hipSuccess) e = hipMemcpyAsync(&ne, d_ne, sizeof(ne), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            dfree(ctx, cflag);
-            dfree(ctx, d_ne);
-            if (e != hipSuccess) { rc = hip_fail(ctx, e, "occupancy", __FILE__, __LINE__); break; }
+            PCP_HIP(ctx, hipMemcpyAsync(&ne, d_ne, sizeof(ne), hipMemcpyDeviceToHost, st));
+            PCP_HIP(ctx, hipStreamSynchronize(st));
+            tmp.free(cflag);
+            tmp.free(d_ne);
             const double occ = (double)n / std::max(1.0, (double)ne);
             bool redo = false;
             if (occ > 12.0) { h *= std::sqrt(4.0 / occ); redo = true; }   // surface-like data
             else if (occ < 1.5) { h *= std::cbrt(4.0 / occ); redo = true; }  // sparser than assumed
             if (redo) continue;
         }
-        if (on_geom && *on_geom && !hooked) {  // the geometry is final (a given cell size, or the
-            hooked = true;                      // refinement is done): let the caller start work
-            if ((rc = (*on_geom)(g))) break;    // that needs only it (overlaps the sort)
+        // the geometry is final (a given cell size, or the refinement is done): let the caller
+        // start work that needs only it (overlaps the sort)
+        if (on_geom && *on_geom && !hooked) {
+            hooked = true;
+            PCP_TRY((*on_geom)(g));
         }
         // + 1 pad entry: the ICP octant pass loads a row's starts as one 3-word vector at the row's
         // first cell, whose third word lies one past the table for a 1-cell row at the last cell
-        if ((rc = dmalloc(ctx, &count, ncells + 2))) break;
+        uint32_t* count = nullptr;
+        PCP_TRY(tmp.get(&count, ncells + 2));
         // ---- stable radix sort by cell id.  fp32: the payload is the point record itself, so
         // the sort output is the cell-ordered point array (no gather).  fp64: the payload is the
         // internal j (FLANN tie order), gathered below.
         uint32_t* key1 = nullptr;
         uint32_t* val1 = nullptr;
-        using V4 = typename Real<T>::V4;
         if (n > 0) {
-            if ((rc = dmalloc(ctx, &key1, n))) break;
-            if (is_f64 && (rc = dmalloc(ctx, &val1, n))) { dfree(ctx, key1); break; }
+            PCP_TRY(tmp.get(&key1, n));
+            if (is_f64) PCP_TRY(tmp.get(&val1, n));
             float4* rec0 = nullptr;
-            if (!is_f64 && (rc = dmalloc(ctx, &rec0, n))) { dfree(ctx, key1); break; }
+            if (!is_f64) PCP_TRY(tmp.get(&rec0, n));
             unsigned bits = 1;
             while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)ncells) bits++;
-            size_t tmp_bytes = 0;
-            void* tmp = nullptr;
+            void* sortmem = nullptr;
             if (is_f64) {
                 hipLaunchKernelGGL(k_cell_keys<T>, dim3(grid_for(n, kB)), dim3(kB), 0, st, g, direct ? xyz : cxyz,
                                    direct ? stride / sizeof(T) : (size_t)3, n, skey, rank, g.dense ? ix->brick : nullptr);
-                PCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, skey, key1, rank, val1, (size_t)n, 0u,
-                                                       bits, st));
-                if (!(rc = dmalloc(ctx, (char**)&tmp, tmp_bytes)))
-                    PCP_HIP(ctx, rocprim::radix_sort_pairs(tmp, tmp_bytes, skey, key1, rank, val1, (size_t)n, 0u,
-                                                           bits, st));
+                PCP_TRY(sort_pairs(tmp, skey, key1, rank, val1, (size_t)n, 0u, bits, &sortmem));
             } else {
                 // no brick marks: the fp32 index serves ICP only, whose dense-grid searches never
                 // read brick occupancy (its brick table stays all-zero = "occupied")
@@ -618,15 +599,10 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
                 else
                     hipLaunchKernelGGL(k_cell_keys_rec, dim3(grid_for(n, kB)), dim3(kB), 0, st, g, (const float*)cxyz,
                                        (size_t)3, (const int32_t*)ix->mapping, n, skey, rec0, nullptr);
-                PCP_HIP(ctx, rocprim::radix_sort_pairs<RecSortConfig>(nullptr, tmp_bytes, skey, key1, rec0, (float4*)ix->pts,
-                                                       (size_t)n, 0u, bits, st));
-                if (!(rc = dmalloc(ctx, (char**)&tmp, tmp_bytes)))
-                    PCP_HIP(ctx, rocprim::radix_sort_pairs<RecSortConfig>(tmp, tmp_bytes, skey, key1, rec0, (float4*)ix->pts,
-                                                           (size_t)n, 0u, bits, st));
+                PCP_TRY(sort_pairs<RecSortConfig>(tmp, skey, key1, rec0, (float4*)ix->pts, (size_t)n, 0u, bits, &sortmem));
             }
-            dfree(ctx, tmp);
-            dfree(ctx, rec0);
-            if (rc) { dfree(ctx, key1); dfree(ctx, val1); break; }
+            tmp.free(sortmem);  // early, like key1 / val1 / lo below: each is dead before the
+            tmp.free(rec0);     // next allocation, which the cache serves from its block
             if (!is_f64)  // pts[n]: a point at infinity (d2 = inf from any finite query) for gathers
                 hipLaunchKernelGGL(k_far_sentinel, dim3(1), dim3(1), 0, st, (float4*)ix->pts, n);
         }
@@ -635,47 +611,38 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
         // ---- chunk boundaries of the sorted keys
         const int64_t nchunk = (ncells + 1 + kChunk - 1) / kChunk;
         uint32_t* lo = nullptr;
-        if ((rc = dmalloc(ctx, &lo, nchunk + 1))) {
-            dfree(ctx, key1); dfree(ctx, val1);
-            break;
-        }
+        PCP_TRY(tmp.get(&lo, nchunk + 1));
         hipLaunchKernelGGL(k_chunk_lo, dim3(grid_for(n + 1, kB, kScanBlocks)), dim3(kB), 0, st, (const uint32_t*)key1, n,
                            nchunk, lo);
         // ---- cell starts straight from the sorted keys (no count array, no scan)
         hipLaunchKernelGGL(k_cell_starts, dim3((unsigned)nchunk), dim3(kB), 0, st, (const uint32_t*)key1,
                            (const uint32_t*)lo, ncells + 1, count);
-        dfree(ctx, lo);
+        tmp.free(lo);
         g.cstart = count;
         if (g.dense && is_f64 && n > 0)
             hipLaunchKernelGGL(k_brick_rows, dim3(grid_for(g.nbricks, kB)), dim3(kB), 0, st, g, ix->brick);
         ix->g = g;
-        ix->cstart = count;
-        count = nullptr;
+        ix->cstart = tmp.release(count);
         if (is_f64) {
-            if ((rc = dmalloc(ctx, &ix->sorted_j, n + 1))) { dfree(ctx, key1); dfree(ctx, val1); break; }
+            PCP_TRY(dmalloc(ctx, &ix->sorted_j, n + 1));
             if (n > 0)
                 hipLaunchKernelGGL(k_gather<T>, dim3(grid_for(n, kB)), dim3(kB), 0, st, direct ? xyz : cxyz,
                                    direct ? stride / sizeof(T) : (size_t)3, (const uint32_t*)val1,
                                    (const int32_t*)ix->mapping, n, (V4*)ix->pts, ix->sorted_j, is_f64);
         }
-        dfree(ctx, key1);
-        dfree(ctx, val1);
+        tmp.free(key1);
+        tmp.free(val1);
         if (is_f64) {
-            if ((rc = dmalloc(ctx, &ix->pos_of_j, n + 1))) break;
+            PCP_TRY(dmalloc(ctx, &ix->pos_of_j, n + 1));
             if (n > 0)
                 hipLaunchKernelGGL(k_inverse, dim3(grid_for(n, kB)), dim3(kB), 0, st,
                                    (const int32_t*)ix->sorted_j, n, ix->pos_of_j);
         }
         break;
     }
-    dfree(ctx, count);
-    dfree(ctx, rank);
-    dfree(ctx, skey);
-    dfree(ctx, cxyz);
-    if (!rc && on_geom && *on_geom && !hooked) rc = (*on_geom)(ix->g);  // (not reached: the loop hooks before its sort)
-    if (rc) return fail(rc);
     PCP_HIP(ctx, hipGetLastError());
     PCP_HIP(ctx, hipStreamSynchronize(st));
+    unbuilt.ix = nullptr;
     *out = ix;
     return PCP_OK;
 }

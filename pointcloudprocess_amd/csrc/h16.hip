@@ -672,15 +672,12 @@ int pcp_h16_radius_fill(pcp_ctx* ctx, const pcp_index* ix, float radius, int64_t
     int32_t* ids = nullptr;
     MxSums* sm = nullptr;
     int64_t* fb = nullptr;
-    struct Free {
-        pcp_ctx* c; int32_t** a; MxSums** b; int64_t** d;
-        ~Free() { dfree(c, *a); dfree(c, *b); dfree(c, *d); }
-    } fr{ctx, &ids, &sm, &fb};
-    if (normals_dev) PCP_TRY(dmalloc(ctx, &sm, (size_t)n_owned));
+    Tmp tmp(ctx);
+    if (normals_dev) PCP_TRY(tmp.get(&sm, (size_t)n_owned));
     // the reported ids: the caller indices (the index's own mapping), or their global ids
     const int32_t* rep_ids = ix->mapping;
     if (global_id_dev) {
-        PCP_TRY(dmalloc(ctx, &ids, (size_t)ix->n));
+        PCP_TRY(tmp.get(&ids, (size_t)ix->n));
         hipLaunchKernelGGL(k_h16_ids, dim3(grid_for(ix->n, kB)), dim3(kB), 0, ctx->stream, (const int32_t*)ix->mapping,
                            global_id_dev, ix->n, ids);
         rep_ids = ids;
@@ -688,7 +685,7 @@ int pcp_h16_radius_fill(pcp_ctx* ctx, const pcp_index* ix, float radius, int64_t
     hipLaunchKernelGGL(k_h16_mx<true>, dim3(mx_blocks(ix->n)), dim3(64), 0, ctx->stream, a, (int32_t*)nullptr,
                        offsets_dev, rep_ids, idx_dev, sm);
     if (normals_dev) {
-        PCP_TRY(dmalloc(ctx, &fb, (size_t)n_owned + 1));
+        PCP_TRY(tmp.get(&fb, (size_t)n_owned + 1));
         uint32_t* nfb = (uint32_t*)(fb + n_owned);
         PCP_HIP(ctx, hipMemsetAsync(nfb, 0, sizeof(uint32_t), ctx->stream));
         hipLaunchKernelGGL(k_h16_mx_planes, dim3(grid_for(n_owned, kB)), dim3(kB), 0, ctx->stream, a,

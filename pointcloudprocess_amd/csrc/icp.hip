@@ -13,7 +13,6 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include "sortcfg.hpp"
@@ -2349,16 +2348,20 @@ namespace {
 // bricks of the target grid, a stable radix sort with the 16-byte records as payload, the count
 // of finite queries
 struct QuerySort {
+    Tmp blocks;
     uint32_t *k0 = nullptr, *k1 = nullptr;
     float4 *r0 = nullptr, *qs = nullptr;
     unsigned long long* d_cnt = nullptr;
-    void* tmp = nullptr;
+    char* tmp = nullptr;
     hipEvent_t done = nullptr;
     int64_t nq = 0;
-    void release(pcp_ctx* ctx) {  // stream-ordered on ctx->stream (after it waited for `done`)
-        dfree(ctx, k0); dfree(ctx, k1); dfree(ctx, r0); dfree(ctx, qs); dfree(ctx, d_cnt); dfree(ctx, tmp);
-        k0 = k1 = nullptr; r0 = qs = nullptr; d_cnt = nullptr; tmp = nullptr;
-        if (done) event_put(ctx, done);
+    explicit QuerySort(pcp_ctx* ctx) : blocks(ctx) {}
+    // The blocks go back to the cache in ctx->stream's order, so only once that stream has waited
+    // for `done` (or the side stream was synchronised after a failure): every path of the two
+    // create functions calls this there, and none leaves the blocks to the guard's scope exit.
+    void release() {
+        blocks.free_all();
+        if (done) event_put(blocks.ctx, done);
         done = nullptr;
     }
 };
@@ -2378,17 +2381,18 @@ int icp_check_grid(pcp_ctx* ctx, const GridDesc& g, int64_t n_target, int64_t nq
 int qsort_launch(pcp_ctx* ctx, hipStream_t st, const GridDesc& g, const float* q, size_t q_stride, int64_t nq,
                  QuerySort& s) {
     s.nq = nq;
-    int rc = PCP_OK;
-    if ((rc = dmalloc(ctx, &s.k0, nq)) || (rc = dmalloc(ctx, &s.k1, nq)) || (rc = dmalloc(ctx, &s.r0, nq)) ||
-        (rc = dmalloc(ctx, &s.qs, nq + 1)) || (rc = dmalloc(ctx, &s.d_cnt, 1)))
-        return rc;
+    PCP_TRY(s.blocks.get(&s.k0, nq));
+    PCP_TRY(s.blocks.get(&s.k1, nq));
+    PCP_TRY(s.blocks.get(&s.r0, nq));
+    PCP_TRY(s.blocks.get(&s.qs, nq + 1));
+    PCP_TRY(s.blocks.get(&s.d_cnt, 1));
     PCP_HIP(ctx, event_get(ctx, &s.done));
     unsigned bits = 1;  // keys are in [0, query_key_end]
     while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)query_key_end(g)) bits++;
     size_t tb = 0;
     if (nq > 0) {
         PCP_HIP(ctx, rocprim::radix_sort_pairs<RecSortConfig>(nullptr, tb, s.k0, s.k1, s.r0, s.qs, (size_t)nq, 0u, bits, st));
-        if ((rc = dmalloc(ctx, (char**)&s.tmp, tb))) return rc;
+        PCP_TRY(s.blocks.get(&s.tmp, tb));
     }
     // Every block the side stream uses is allocated above, before `go` is recorded: a block the
     // context cache hands out after that point could still be in use by main-stream work the side
@@ -2414,14 +2418,14 @@ int qsort_launch(pcp_ctx* ctx, hipStream_t st, const GridDesc& g, const float* q
 }
 
 // the sorted records -> 12-byte xyz + original indices, on ctx->stream after the sort
-int qsort_finish(pcp_ctx* ctx, QuerySort& s, QXyz** q3, int32_t** qi, int64_t* nfin) {
+int qsort_finish(pcp_ctx* ctx, Tmp& tmp, QuerySort& s, QXyz** q3, int32_t** qi, int64_t* nfin) {
     PCP_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.done, 0));
     unsigned long long hc = 0;
     PCP_HIP(ctx, hipMemcpyAsync(&hc, s.d_cnt, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream));
     PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *nfin = (int64_t)hc;
-    int rc = PCP_OK;
-    if ((rc = dmalloc(ctx, q3, s.nq + 1)) || (rc = dmalloc(ctx, qi, s.nq + 1))) return rc;
+    PCP_TRY(tmp.get(q3, s.nq + 1));
+    PCP_TRY(tmp.get(qi, s.nq + 1));
     if (*nfin > 0)
         hipLaunchKernelGGL(k_split_queries, dim3(grid_for(*nfin, 256)), dim3(256), 0, ctx->stream,
                            (const float4*)s.qs, *nfin, *q3, *qi);
@@ -2514,19 +2518,16 @@ int pcp_icp_create(pcp_ctx* ctx, const pcp_index* target, const float* q, size_t
     if (q_stride == 0) q_stride = 3 * sizeof(float);
     if (q_stride % sizeof(float)) return pcp::set_error(ctx, PCP_ERR_ARG, "query stride must be whole floats");
     PCP_TRY(pcp::icp_check_grid(ctx, target->g, target->n, nq));
-    pcp::QuerySort s;
+    pcp::Tmp tmp(ctx);  // q3, qi until the handle owns them
+    pcp::QuerySort s(ctx);
     pcp::QXyz* q3 = nullptr;
     int32_t* qi = nullptr;
     int64_t nfin = 0;
     int rc = pcp::qsort_launch(ctx, ctx->stream, target->g, q, q_stride, nq, s);
-    if (!rc) rc = pcp::qsort_finish(ctx, s, &q3, &qi, &nfin);
-    s.release(ctx);
-    if (rc) {
-        pcp::dfree(ctx, q3);
-        pcp::dfree(ctx, qi);
-        return rc;
-    }
-    return pcp::icp_make(ctx, target, q3, qi, nfin, nq, out);
+    if (!rc) rc = pcp::qsort_finish(ctx, tmp, s, &q3, &qi, &nfin);
+    s.release();  // early: the handle's buffers are served from these blocks
+    if (rc) return rc;
+    return pcp::icp_make(ctx, target, tmp.release(q3), tmp.release(qi), nfin, nq, out);
 }
 
 int pcp_icp_create_with_target(pcp_ctx* ctx, const float* target_xyz, size_t t_stride, int64_t n_target,
@@ -2541,7 +2542,8 @@ int pcp_icp_create_with_target(pcp_ctx* ctx, const float* target_xyz, size_t t_s
     if (q_stride % sizeof(float)) return pcp::set_error(ctx, PCP_ERR_ARG, "query stride must be whole floats");
     // the query sort needs only the target grid's geometry: it runs on the side stream while the
     // target's cell sort runs on the main stream (two independent radix sorts overlapped)
-    pcp::QuerySort s;
+    pcp::Tmp tmp(ctx);  // q3, qi until the handle owns them
+    pcp::QuerySort s(ctx);
     bool launched = false;
     const pcp::GeomHook hook = [&](const pcp::GridDesc& g) -> int {
         PCP_TRY(pcp::icp_check_grid(ctx, g, n_target, nq));
@@ -2556,14 +2558,10 @@ int pcp_icp_create_with_target(pcp_ctx* ctx, const float* target_xyz, size_t t_s
     int32_t* qi = nullptr;
     int64_t nfin = 0;
     if (!rc && !launched) rc = pcp::qsort_launch(ctx, ctx->stream, ix->g, q, q_stride, nq, s);
-    if (!rc) rc = pcp::qsort_finish(ctx, s, &q3, &qi, &nfin);
+    if (!rc) rc = pcp::qsort_finish(ctx, tmp, s, &q3, &qi, &nfin);
     if (rc && launched) (void)hipStreamSynchronize(ctx->side);  // the side stream's work is over
-    s.release(ctx);
-    if (!rc) rc = pcp::icp_make(ctx, ix, q3, qi, nfin, nq, icp_out);
-    else {
-        pcp::dfree(ctx, q3);
-        pcp::dfree(ctx, qi);
-    }
+    s.release();  // early: the handle's buffers are served from these blocks
+    if (!rc) rc = pcp::icp_make(ctx, ix, tmp.release(q3), tmp.release(qi), nfin, nq, icp_out);
     if (rc) {
         if (ix) pcp_index_destroy(ix);
         return rc;
@@ -2583,14 +2581,13 @@ int pcp_icp_set_options(pcp_icp* icp, int oct_lanes_first, int oct_lanes_list, i
     if (widen && icp->launches > 0)
         return pcp::set_error(ctx, PCP_ERR_ARG, "PCP_ICP_OPT_WIDE_CACHE only before the handle's first launch");
     if (widen) {  // re-create the records in the 16-byte form
+        pcp::Tmp tmp(ctx);
         uint32_t* w = nullptr;
-        if (int rc = pcp::dmalloc(ctx, &w, (size_t)(icp->nq + 1) * 4)) return rc;
-        if (hipMemsetAsync(w, 0xff, (size_t)(icp->nq + 1) * 16, ctx->stream) != hipSuccess) {
-            pcp::dfree(ctx, w);
+        PCP_TRY(tmp.get(&w, (size_t)(icp->nq + 1) * 4));
+        if (hipMemsetAsync(w, 0xff, (size_t)(icp->nq + 1) * 16, ctx->stream) != hipSuccess)
             return pcp::set_error(ctx, PCP_ERR_HIP, "pcp_icp_set_options: memset");
-        }
         pcp::dfree(ctx, icp->cand);
-        icp->cand = w;
+        icp->cand = tmp.release(w);
         icp->narrow = false;
     }
     if (icp->gexec) {  // captured with the old lanes / flags

@@ -15,7 +15,7 @@
 #include <cmath>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
+#include "sortcfg.hpp"
 
 #include "grid.hpp"
 #include "topk.hpp"
@@ -1767,17 +1767,14 @@ int check_f64_index(pcp_ctx* ctx, const pcp_index* ix) {
 
 int centroid_aos48_dev(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, double c[4], uint32_t* count);
 
-// deferred-query list of one call (returned to the context's cache on scope exit)
+// deferred-query list of one call (blocks of the call's Tmp)
 struct FarBuf {
     FarList f{nullptr, nullptr};
-    pcp_ctx* ctx = nullptr;
-    ~FarBuf() { dfree(ctx, f.list); dfree(ctx, f.count); dfree(ctx, f.ub); }
-    int alloc(pcp_ctx* c, int64_t n, bool with_ub = false) {
-        ctx = c;
-        PCP_TRY(dmalloc(ctx, &f.list, n));
-        PCP_TRY(dmalloc(ctx, &f.count, 1));
-        if (with_ub) PCP_TRY(dmalloc(ctx, &f.ub, n));
-        PCP_HIP(ctx, hipMemsetAsync(f.count, 0, sizeof(uint32_t), ctx->stream));
+    int alloc(Tmp& tmp, int64_t n, bool with_ub = false) {
+        PCP_TRY(tmp.get(&f.list, n));
+        PCP_TRY(tmp.get(&f.count, 1));
+        if (with_ub) PCP_TRY(tmp.get(&f.ub, n));
+        PCP_HIP(tmp.ctx, hipMemsetAsync(f.count, 0, sizeof(uint32_t), tmp.ctx->stream));
         return PCP_OK;
     }
 };
@@ -1804,8 +1801,9 @@ int pcp_knn(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, 
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     const double mc = cell_margin64(ix->g);
     const double4* pts = (const double4*)ix->pts;
+    Tmp tmp(ctx);
     FarBuf fb;
-    PCP_TRY(fb.alloc(ctx, nq));
+    PCP_TRY(fb.alloc(tmp, nq));
 #define LAUNCH_KNN(KV)                                                                                          \
     hipLaunchKernelGGL((k_knn<KV, false>), dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,  \
                        ix->identity, q, qstride, nq, k, kk, mc, oidx, od2, fb.f);                                  \
@@ -1841,12 +1839,13 @@ int pcp_radius_count(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t 
     const double4* pts = (const double4*)ix->pts;
     const uint32_t cap = radius_cap(ix, max_nn);
     const double mc = cell_margin64(ix->g);
+    Tmp tmp(ctx);
     if (radius_needs_far(ix, radius)) {
         hipLaunchKernelGGL(k_radius_count<true>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
                            nq, radius * radius, cap, mc, ocnt, FarList{nullptr, nullptr});
     } else {
         FarBuf fb;
-        PCP_TRY(fb.alloc(ctx, nq));
+        PCP_TRY(fb.alloc(tmp, nq));
         hipLaunchKernelGGL(k_radius_count<false>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q,
                            qstride, nq, radius * radius, cap, mc, ocnt, fb.f);
         hipLaunchKernelGGL(k_radius_count<true>, dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
@@ -1868,12 +1867,13 @@ int pcp_radius_fill(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t q
     const double4* pts = (const double4*)ix->pts;
     const double mc = cell_margin64(ix->g);
     const uint32_t cap = radius_cap(ix, max_nn);
+    Tmp tmp(ctx);
     if (radius_needs_far(ix, radius)) {
         hipLaunchKernelGGL(k_radius_fill<true>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
                            nq, radius * radius, cap, mc, off, oidx, od2, FarList{nullptr, nullptr});
     } else {
         FarBuf fb;
-        PCP_TRY(fb.alloc(ctx, nq));
+        PCP_TRY(fb.alloc(tmp, nq));
         hipLaunchKernelGGL(k_radius_fill<false>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q,
                            qstride, nq, radius * radius, cap, mc, off, oidx, od2, fb.f);
         hipLaunchKernelGGL(k_radius_fill<true>, dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
@@ -1899,30 +1899,23 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
     if (!ctx->nrm_deferred) PCP_HIP(ctx, hipMalloc(&ctx->nrm_deferred, 2 * sizeof(uint32_t)));
     const double mc = cell_margin64(ix->g);
     const double4* pts = (const double4*)ix->pts;
+    Tmp tmp(ctx);
     FarBuf fb;
-    PCP_TRY(fb.alloc(ctx, ix->n, true));
+    PCP_TRY(fb.alloc(tmp, ix->n, true));
     const int tile_R = kk <= 8 ? 1 : 2;  // the tile's window half-width in cells
     if (ix->g.dense) {
         unsigned long long* st = nullptr;  // per-phase counters of profiling builds (PCP_NORMALS_STATS)
 #if PCP_NORMALS_STATS
-        PCP_TRY(dmalloc(ctx, &st, 24));
+        PCP_TRY(tmp.get(&st, 24));
         PCP_HIP(ctx, hipMemsetAsync(st, 0, 24 * sizeof(unsigned long long), ctx->stream));
 #endif
         const unsigned nbt = (unsigned)std::min<int64_t>((ix->n + 63) / 64, 1 << 20);
         // brick order of the queries: (brick key, sorted position) radix-sorted
-        uint32_t *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *order = nullptr;
-        void* tmp = nullptr;
-        size_t tb = 0;
-        struct Free {
-            pcp_ctx* c;
-            uint32_t **a, **b, **d, **e;
-            void** t;
-            ~Free() { dfree(c, *a); dfree(c, *b); dfree(c, *d); dfree(c, *e); dfree(c, (char*)*t); }
-        } fr{ctx, &k0, &k1, &v0, &order, &tmp};
-        PCP_TRY(dmalloc(ctx, &k0, ix->n));
-        PCP_TRY(dmalloc(ctx, &k1, ix->n));
-        PCP_TRY(dmalloc(ctx, &v0, ix->n));
-        PCP_TRY(dmalloc(ctx, &order, ix->n));
+        uint32_t *k0, *k1, *v0, *order;
+        PCP_TRY(tmp.get(&k0, ix->n));
+        PCP_TRY(tmp.get(&k1, ix->n));
+        PCP_TRY(tmp.get(&v0, ix->n));
+        PCP_TRY(tmp.get(&order, ix->n));
         const int64_t nbr = (int64_t)((ix->g.n[0] + 7) >> kTileBrick) * ((ix->g.n[1] + 7) >> kTileBrick) *
                             ((ix->g.n[2] + 7) >> kTileBrick);
         unsigned bits = 1;
@@ -1933,11 +1926,9 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
         hipLaunchKernelGGL(k_brick_keys, dim3(blocks_for(ix->n)), dim3(kB), 0, ctx->stream, ix->g, pts, ix->n, lb, k0,
                            v0);
         bits += (unsigned)lb;
-        PCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, k0, k1, v0, order, (size_t)ix->n, 0u, bits, ctx->stream));
-        PCP_TRY(dmalloc(ctx, (char**)&tmp, tb));
-        PCP_HIP(ctx, rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, order, (size_t)ix->n, 0u, bits, ctx->stream));
+        PCP_TRY(sort_pairs(tmp, k0, k1, v0, order, (size_t)ix->n, 0u, bits));
         FarBuf fb2;  // the near pass's own deferred queries
-        PCP_TRY(fb2.alloc(ctx, ix->n, true));
+        PCP_TRY(fb2.alloc(tmp, ix->n, true));
         // the tile's uncertified queries: the lane-per-query near pass (cell rings), its own
         // deferrals then the wave-per-query pass (PCP_NORMALS_NEAR_DEFAULT; 0: all of them straight
         // to the wave-per-query pass, measured slower)
@@ -1979,7 +1970,6 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
                     (long long)ix->n, k, c1, h[0], h[2], h[1], c2, d[0], d[0] ? (double)d[1] / d[0] : 0.0, d[2],
                     d[0] ? (double)d[3] / d[0] : 0.0, d[4], d[11], d[12], d[13], d[14], d[15],
                     __builtin_bit_cast(double, d[5]), __builtin_bit_cast(double, d[6]), __builtin_bit_cast(double, d[7]));
-            dfree(ctx, st);
         }
 #endif
         return PCP_OK;
@@ -2048,11 +2038,12 @@ int pcp_nearest_query(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t
     double* pd = nullptr;
     int64_t* pi = nullptr;
     const unsigned nb = grid_for(nq, kB, 1024);
-    int rc = dmalloc(ctx, &idx, nq);
-    if (!rc) rc = dmalloc(ctx, &d2, nq);
-    if (!rc) rc = dmalloc(ctx, &pd, nb);
-    if (!rc) rc = dmalloc(ctx, &pi, nb);
-    if (!rc) rc = pcp_knn(ctx, ix, q, qstride, nq, 1, idx, d2);
+    Tmp tmp(ctx);
+    PCP_TRY(tmp.get(&idx, nq));
+    PCP_TRY(tmp.get(&d2, nq));
+    PCP_TRY(tmp.get(&pd, nb));
+    PCP_TRY(tmp.get(&pi, nb));
+    int rc = pcp_knn(ctx, ix, q, qstride, nq, 1, idx, d2);
     if (!rc) {
         hipLaunchKernelGGL(k_argmin_d2, dim3(nb), dim3(kB), 0, ctx->stream, d2, nq, pd, pi);
         std::vector<double> hd(nb);
@@ -2068,7 +2059,6 @@ int pcp_nearest_query(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t
             if (hd[b] < bd || (hd[b] == bd && hi[b] < bi)) { bd = hd[b]; bi = hi[b]; }
         if (!rc && bd < init_bound) { *best_d2 = bd; *best_q = bi; }
     }
-    dfree(ctx, idx); dfree(ctx, d2); dfree(ctx, pd); dfree(ctx, pi);
     return rc;
 }
 
@@ -2087,7 +2077,8 @@ int pcp_knn_lod(pcp_ctx* ctx, const void* cloud, int64_t n, const void* q, int64
     PCP_TRY(centroid_aos48_dev(ctx, cloud, n, 1, c, &cnt));
     const int ci0 = (int)c[0], ci1 = (int)c[1], ci2 = (int)c[2];
     float* v = nullptr;
-    PCP_TRY(dmalloc(ctx, &v, 3 * (size_t)n));
+    Tmp tmp(ctx);
+    PCP_TRY(tmp.get(&v, 3 * (size_t)n));
     hipLaunchKernelGGL(k_lod_vertices, dim3(blocks_for(n)), dim3(kB), 0, ctx->stream, (const char*)cloud, n, ci0, ci1,
                        ci2, v);
     pcp_index* fi = nullptr;
@@ -2116,7 +2107,6 @@ int pcp_knn_lod(pcp_ctx* ctx, const void* cloud, int64_t n, const void* q, int64
     }
     if (fi) pcp_index_destroy(fi);
     if (di) pcp_index_destroy(di);
-    dfree(ctx, v);
     return rc;
 }
 

@@ -499,12 +499,14 @@ int pcp_knn_bruteforce(pcp_ctx* ctx, const double* t, size_t tstride, int64_t nt
     uint32_t* fbc = nullptr;
     const unsigned npb = grid_for(nt > 0 ? nt : 1, 256, 1024);
     const int64_t ntpad = std::max<int64_t>((nt + kTile - 1) / kTile * kTile, 1);  // whole tiles (LDS-DMA)
-    int rc = dmalloc(ctx, &t4, 4 * (size_t)ntpad);
-    if (!rc) rc = dmalloc(ctx, &part, 2 * (size_t)npb);
-    if (!rc) rc = dmalloc(ctx, &fb, nq);
-    if (!rc) rc = dmalloc(ctx, &fbc, 1);
+    Tmp tmp(ctx);
+    PCP_TRY(tmp.get(&t4, 4 * (size_t)ntpad));
+    PCP_TRY(tmp.get(&part, 2 * (size_t)npb));
+    PCP_TRY(tmp.get(&fb, nq));
+    PCP_TRY(tmp.get(&fbc, 1));
+    int rc = PCP_OK;
     double pmax2 = 0.0, nfin = 0.0;
-    if (!rc && nt > 0) {
+    if (nt > 0) {
         hipLaunchKernelGGL(k_bf_targets, dim3(npb), dim3(256), 0, st, t, tstride, nt, t4, part);
         if (ntpad > nt)
             hipLaunchKernelGGL(k_bf_pad, dim3(1), dim3(256), 0, st, t4, nt, ntpad);
@@ -556,10 +558,6 @@ int pcp_knn_bruteforce(pcp_ctx* ctx, const double* t, size_t tstride, int64_t nt
             if (e != hipSuccess) rc = hip_fail(ctx, e, "k_bf_mfma", __FILE__, __LINE__);
         }
     }
-    dfree(ctx, t4);
-    dfree(ctx, part);
-    dfree(ctx, fb);
-    dfree(ctx, fbc);
     return rc;
 }
 

@@ -98,12 +98,9 @@ extern "C" int pcp_region_growing(pcp_ctx* ctx, const pcp_index* index, const do
     const int k = kRgK;
     int32_t* nbr = nullptr;
     uint64_t* mask = nullptr;
-    PCP_TRY(dmalloc(ctx, &nbr, (size_t)n * k));
-    PCP_TRY(dmalloc(ctx, &mask, (size_t)n));
-    struct Free {
-        pcp_ctx* c; void* a; void* b;
-        ~Free() { dfree(c, a); dfree(c, b); }
-    } fr{ctx, nbr, mask};
+    Tmp tmp(ctx);
+    PCP_TRY(tmp.get(&nbr, (size_t)n * k));
+    PCP_TRY(tmp.get(&mask, (size_t)n));
     PCP_TRY(pcp_knn(ctx, index, xyz, stride, n, k, nbr, nullptr));
     hipLaunchKernelGGL(k_rg_edges, dim3(grid_for(n, 256, 1 << 16)), dim3(256), 0, ctx->stream, props,
                        (const char*)xyz, stride, n, nbr, k, distance_t, mask);

@@ -43,6 +43,12 @@ class Context:
     def sync(self):
         self.check(self.lib.pcp_sync(self.h))
 
+    def alloc_stats(self):
+        """(blocks handed out, their bytes, peak bytes, hipMalloc calls) of the internal allocator."""
+        out = (C.c_int64 * 4)()
+        self.check(self.lib.pcp_ctx_alloc_stats(self.h, out))
+        return tuple(out)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.pcp_ctx_destroy(self.h)
