@@ -226,7 +226,8 @@ int pcp_normals_knn_last_deferred(pcp_ctx* ctx, int64_t* tile_deferred, int64_t*
 /* F3: CalculateFeature::calculate_plan_parameter_rpca(cloud, radius (unused), Pr, epi)
  * (calculate_feature.cpp:208-368; the pipeline's normals entry, static.cpp:17) over the
  * caller's kNN rows knn_idx_dev (n x k int32, k <= 20, ascending d2, -1 padded: pcp_knn of
- * the cloud's own points with k = 20).  Deterministic contract (the reference seeds rand()
+ * the cloud's own points with k = 20; N of a row is its leading run of non-negative indices,
+ * nothing behind the first -1 is read).  Deterministic contract (the reference seeds rand()
  * with time(NULL)): the 3 neighbours of iteration i of point j are
  * splitmix64(seed, j, i, slot) % N; sorts are stable; min_value ties keep the earlier
  * iteration.  segment_id and dis_from_point_plane are written 0 (the reference leaves them

@@ -84,7 +84,9 @@ __global__ __launch_bounds__(kB) void k_rpca(const double* xyz, size_t stride_d,
     for (int64_t j = (int64_t)blockIdx.x * kW + w; j < n; j += nwaves) {
         const int32_t nb = lane < k ? knn[j * k + lane] : -1;
         const uint64_t have = __ballot(lane < kK && nb >= 0);
-        const int N = __popcll(have);  // rows are -1 padded after the found neighbours
+        // N is the leading run of found neighbours (rows are -1 padded after it; pcp.h): an index
+        // behind a -1 is never loaded.  Lanes >= min(k, kK) are clear in `have`, so ~have != 0.
+        const int N = __ffsll((unsigned long long)~have) - 1;
         if (lane < N) {
             const double* p = xyz + (size_t)nb * stride_d;
             for (int a = 0; a < 3; a++) {
