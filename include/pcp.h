@@ -406,6 +406,75 @@ int pcp_get_rot_icp(pcp_ctx* ctx, const void* src_aos48_dev, int64_t ns, int src
                     double mat_rot_host[16], float rmax, int iters, int do_scale,
                     double cell_size, float* err);
 
+/* ----------------------------------------------------------------------- I2: point-to-plane ICP
+ * The build's OWN point-to-plane contract, NOT parity with trimesh2: the reference registers
+ * through trimesh2's ICP() (point_cloud_helper.cpp:127), a library that is absent here; by its
+ * published source it minimises point-to-plane distances over normals it estimates itself.  The
+ * entries below minimise sum (n_j . (T q_i - p_j))^2 over the exact nearest-neighbour pairs
+ * (i, j) of the search above, with the per-point PCA normals of pcp_normals_knn; nothing in
+ * them restates trimesh2's weighting, sampling or rejection.
+ *
+ * Plane table (pcp_icp_planes): one 32-byte record {px,py,pz,0, nx,ny,nz,0} per target point at
+ * the target's CALLER index, so a pair costs one 32-byte gather.  target_xyz_dev: fp32 points
+ * (stride 0 = 12); normals_dev: packed fp32 normals (stride 0 = 12) or the rows of
+ * pcp_normals_knn (stride 24, normal at offset 0).  A record is INVALID, and stored with a zero
+ * normal, when !(nx^2 + ny^2 + nz^2 >= 0.25) in fp32 (the {0,0,0,1,..} rows pcp_normals_knn
+ * writes for dropped points, a NaN normal) or when its point or normal is not finite.
+ * pcp_icp_planes_valid counts the other records (pcp_icp_planes_create waits for that count).
+ * The handle holds a reference on its context like an index; it owns one allocator block.
+ *
+ * pcp_icp_accumulate_plane: the 30 accumulators over the queries i < nq (original order) whose
+ * key (pcp_icp_keys_dev) is not INT64_MAX, whose target index j = key & 0xffffffff is < the
+ * table's size (a larger index is skipped, never read) and whose record j is valid:
+ *   q' = R q + t with the pose cast to fp32 and the fp32 fmaf chain of the point-to-point loop;
+ *   p, n widened to fp64; c = q' x n, r = n . (q' - p) in fp64 without contraction; J = (c, n);
+ *   [0] pairs, [1..21] upper triangle of sum J J^T row-major (00..05, 11..15, .., 55),
+ *   [22..27] sum r J, [28] sum r^2, [29] sum of the keys' fp32 d2.
+ * nq == 0 writes 30 zeros.  The result is a plain sum (negating every normal leaves it bit for
+ * bit unchanged), so target-sharded callers may all-reduce it before the solve.
+ *
+ * pcp_icp_solve_plane (host memory only): minimises sum (r + J . x)^2 over x = (omega, t), i.e.
+ * A x = -b, with the rotation unknowns scaled by s = sqrt(trace(A_ww) / trace(A_tt)) (the RMS
+ * lever arm), the system divided by its largest diagonal entry and factored by unpivoted LDL^T.
+ * It FAILS (PCP_ERR_ICP, dT = identity) when n < 6, trace(A_tt) == 0 or any pivot <= 1e-10:
+ * numerically singular systems only (one exact plane, two orthogonal planes), not thin ones.
+ * dT = [exp([omega]x) by Rodrigues, t], exactly rigid.
+ * pcp_icp_solve_plane_dev: the same in one device thread, T_dev <- dT * T_dev; stats_dev (4
+ * doubles, zeroed by the caller) = [status (0 ok, -1 failed: T frozen from then on),
+ * sqrt([29] / n) = RMS point distance, sqrt([28] / n) = RMS plane distance, iterations solved].
+ * pcp_icp_run_plane_dev = iters x (pcp_icp_keys_dev at offset 0, accumulate, solve) on the
+ * context's stream with no host round trip; nq must be the handle's query count and the table's
+ * size the target index's caller size (PCP_ERR_ARG otherwise). */
+#define PCP_ICP_PLANE_ACC 30
+typedef struct pcp_icp_planes pcp_icp_planes;  /* packed {p, n} table of an ICP target */
+
+int pcp_icp_planes_create(pcp_ctx* ctx, const float* target_xyz_dev, size_t t_stride_bytes,
+                          const float* normals_dev, size_t n_stride_bytes, int64_t n,
+                          pcp_icp_planes** out);
+int pcp_icp_planes_destroy(pcp_icp_planes* planes);
+int64_t pcp_icp_planes_size(const pcp_icp_planes* planes);
+int64_t pcp_icp_planes_valid(const pcp_icp_planes* planes);  /* records with a usable normal */
+
+int pcp_icp_accumulate_plane(pcp_ctx* ctx, const double* T_dev, const float* q_dev, size_t q_stride_bytes,
+                             int64_t nq, const uint64_t* keys_dev, const pcp_icp_planes* planes,
+                             double* acc_dev /* 30 */);
+int pcp_icp_solve_plane(const double acc_host[30], double dT_host[16]);
+int pcp_icp_solve_plane_dev(pcp_ctx* ctx, const double* acc_dev, double* T_dev, double* stats_dev /* 4 */);
+int pcp_icp_run_plane_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
+                          size_t q_stride_bytes, int64_t nq, double* T_dev, float rmax, int iters,
+                          double* stats_dev);
+/* pcp_get_rot_icp with the point-to-plane loop above (again the build's own contract, not
+ * trimesh2's): joint centroid and fp32 centring as pcp_get_rot_icp, an fp64 index over src
+ * (automatic cell size) for pcp_normals_knn(normals_k) -- normals are translation-invariant --
+ * the plane table, pcp_icp_run_plane_dev from the identity, the same un-centring of t.  Non-finite
+ * src points keep their caller index and get an invalid record.  rmax <= 0 -> PCP_ERR_UNSUPPORTED;
+ * normals_k errors are pcp_normals_knn's.  *err = RMS point distance (m) of the accepted pairs of
+ * the last iteration; a failed solve returns PCP_OK with *err = -1. */
+int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src_aos48_dev, int64_t ns, int src_is_dense,
+                          const void* temp_aos48_dev, int64_t nt, int temp_is_dense,
+                          double mat_rot_host[16], float rmax, int iters, int normals_k,
+                          double cell_size, float* err);
+
 /* ----------------------------------------------------------------------- I4: pose lines
  * Host-only (no device work): n frames' poses as row-major 4x4 doubles, rots[16 * i].
  *

@@ -109,6 +109,16 @@ SIGNATURES = [
     ("pcp_build_id", C.c_char_p, []),
     ("pcp_get_rot_icp", _i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _P(_f64), _f32, _i32, _i32,
                                _f64, _P(_f32)]),
+    ("pcp_icp_planes_create", _i32, [_vp, _vp, _sz, _vp, _sz, _i64, _P(_vp)]),
+    ("pcp_icp_planes_destroy", _i32, [_vp]),
+    ("pcp_icp_planes_size", _i64, [_vp]),
+    ("pcp_icp_planes_valid", _i64, [_vp]),
+    ("pcp_icp_accumulate_plane", _i32, [_vp, _vp, _vp, _sz, _i64, _vp, _vp, _vp]),
+    ("pcp_icp_solve_plane", _i32, [_P(_f64), _P(_f64)]),
+    ("pcp_icp_solve_plane_dev", _i32, [_vp, _vp, _vp, _vp]),
+    ("pcp_icp_run_plane_dev", _i32, [_vp, _vp, _vp, _vp, _sz, _i64, _vp, _f32, _i32, _vp]),
+    ("pcp_get_rot_icp_plane", _i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _P(_f64), _f32, _i32, _i32,
+                                     _f64, _P(_f32)]),
 ]
 
 _lib = None

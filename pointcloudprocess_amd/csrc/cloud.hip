@@ -453,4 +453,76 @@ int pcp_get_rot_icp(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, co
     return rc;
 }
 
+// pcp_get_rot_icp's staging (joint centroid, fp32 centring, fp32 target index, query set, the
+// un-centring of t) around the point-to-plane device loop: the build's own contract (pcp.h, I2)
+int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, const void* tmp, int64_t nt,
+                          int tmp_dense, double M[16], float rmax, int iters, int normals_k, double cell_size,
+                          float* err) {
+    if (!ctx || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tmp) || !M || iters < 0)
+        return set_error(ctx, PCP_ERR_ARG, "pcp_get_rot_icp_plane: bad arguments");
+    if (err) *err = -1.0f;
+    for (int i = 0; i < 16; i++) M[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    if (!(rmax > 0.f))
+        return set_error(ctx, PCP_ERR_UNSUPPORTED,
+                         "pcp_get_rot_icp_plane: rmax must be > 0 (trimesh2's automatic maxdist = 0 is not provided)");
+    if (ns == 0 || nt == 0) return PCP_OK;  // ICP fails: err < 0
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    double s[4];
+    const int joint_dense = src_dense && tmp_dense;
+    PCP_TRY(seqfold_aos48(ctx, src, ns, tmp, nt, joint_dense, s));
+    const double dn = joint_dense ? (double)(ns + nt) : (double)(uint32_t)s[3];
+    const double c[3] = {s[0] / dn, s[1] / dn, s[2] / dn};
+    float* fs = nullptr;
+    float* ft = nullptr;
+    pcp_plane* nrm = nullptr;
+    double* pose = nullptr;  // T (16), stats (4)
+    Tmp bufs(ctx);
+    PCP_TRY(bufs.get(&fs, 3 * (size_t)ns));
+    PCP_TRY(bufs.get(&ft, 3 * (size_t)nt));
+    PCP_TRY(bufs.get(&pose, 20));
+    // handles are destroyed on every path, the ICP handle before its target index
+    struct Handles {
+        pcp_index* ix = nullptr;
+        pcp_index* ix64 = nullptr;
+        pcp_icp* icp = nullptr;
+        pcp_icp_planes* planes = nullptr;
+        ~Handles() {
+            if (planes) pcp_icp_planes_destroy(planes);
+            if (icp) pcp_icp_destroy(icp);
+            if (ix64) pcp_index_destroy(ix64);
+            if (ix) pcp_index_destroy(ix);
+        }
+    } h;
+    hipLaunchKernelGGL(k_centre_f32, dim3(grid_for(ns, kB)), dim3(kB), 0, ctx->stream, (const P48*)src, ns, c[0], c[1],
+                       c[2], fs);
+    hipLaunchKernelGGL(k_centre_f32, dim3(grid_for(nt, kB)), dim3(kB), 0, ctx->stream, (const P48*)tmp, nt, c[0], c[1],
+                       c[2], ft);
+    PCP_TRY(pcp_index_build_f32(ctx, fs, 3 * sizeof(float), ns, cell_size, &h.ix));
+    PCP_TRY(pcp_icp_create(ctx, h.ix, ft, 3 * sizeof(float), nt, &h.icp));
+    // normals over the caller's fp64 points (translation-invariant, so not the centred copy); the
+    // index drops the same non-finite points as the fp32 one and keeps the caller indices
+    PCP_TRY(pcp_index_build_f64(ctx, (const double*)src, PCP_AOS48_STRIDE, ns, nullptr, 0, 0.0, &h.ix64));
+    PCP_TRY(bufs.get(&nrm, (size_t)ns));
+    PCP_TRY(pcp_normals_knn(ctx, h.ix64, normals_k, nrm, ns));
+    pcp_index_destroy(h.ix64);
+    h.ix64 = nullptr;
+    PCP_TRY(pcp_icp_planes_create(ctx, fs, 3 * sizeof(float), (const float*)nrm, sizeof(pcp_plane), ns, &h.planes));
+    bufs.free(nrm);
+    double T[20] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0};
+    PCP_HIP(ctx, hipMemcpyAsync(pose, T, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    PCP_TRY(pcp_icp_run_plane_dev(ctx, h.icp, h.planes, ft, 3 * sizeof(float), nt, pose, rmax, iters, pose + 16));
+    PCP_HIP(ctx, hipMemcpyAsync(T, pose, sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(M, T, 16 * sizeof(double));
+    for (int r = 0; r < 3; r++) {  // t' = (t - R c) + c, as pcp_get_rot_icp
+        double rcv = M[4 * r] * c[0];
+        rcv = rcv + M[4 * r + 1] * c[1];
+        rcv = rcv + M[4 * r + 2] * c[2];
+        M[4 * r + 3] = (M[4 * r + 3] - rcv) + c[r];
+    }
+    // stats: a failed solve (or no solved iteration) reports err = -1, as pcp_get_rot_icp does
+    if (err) *err = (T[16] < 0 || T[19] < 1.0) ? -1.0f : (float)T[17];
+    return PCP_OK;
+}
+
 }  // extern "C"

@@ -152,6 +152,11 @@ __device__ __forceinline__ bool finite3(double x, double y, double z) {
 int seqfold_aos48(pcp_ctx* ctx, const void* p0, int64_t n0, const void* p1, int64_t n1, int is_dense,
                   double s_host[4]);
 
+// What code outside icp.hip may know of an ICP handle (icp.hip): its target index and the number
+// of queries passed to pcp_icp_create (the length of a pcp_icp_keys_dev buffer).
+const pcp_index* icp_target(const pcp_icp* icp);
+int64_t icp_query_count(const pcp_icp* icp);
+
 // Exclusive scan of `n` uint32 values in place (values' total must fit uint32).
 // Returns the total through *total_dev (device, optional) and *total_host (optional, syncs).
 int scan_u32_inplace(pcp_ctx* ctx, uint32_t* data, int64_t n, uint32_t* total_host);

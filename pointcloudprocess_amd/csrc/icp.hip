@@ -2505,6 +2505,11 @@ int icp_make(pcp_ctx* ctx, const pcp_index* target, QXyz* q3, int32_t* qi, int64
 }
 
 }  // namespace
+
+// common.hpp: the handle's facts the point-to-plane loop (icp_plane.hip) checks its arguments by
+const pcp_index* icp_target(const pcp_icp* icp) { return icp->target; }
+int64_t icp_query_count(const pcp_icp* icp) { return icp->nq_in; }
+
 }  // namespace pcp
 
 extern "C" {

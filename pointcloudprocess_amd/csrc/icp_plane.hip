@@ -1,0 +1,390 @@
+// Point-to-plane ICP (include/pcp.h, I2): the build's own contract, not trimesh2's.  The exact
+// correspondence search stays in icp.hip; this file takes its per-query winner keys
+// (pcp_icp_keys_dev) and does the minimisation: a packed {point, normal} table of the target,
+// the 30 accumulators of sum (n . (T q - p))^2 linearised at the pose, the scaled 6x6 LDL^T
+// solve, and the device loop around the three.
+//
+// The accumulation's cost is its gather: one 32-byte record per pair at a data-dependent index,
+// both halves in one 64-byte line (two arrays would cost two lines).  Everything else streams.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "common.hpp"
+
+struct pcp_icp_planes {
+    pcp_ctx* owner = nullptr;  // the creating context: owns rec (a lifetime reference)
+    int64_t n = 0;             // records = the target's caller size
+    int64_t valid = 0;         // records with a usable normal
+    float4* rec = nullptr;     // 2 * n: {px,py,pz,0}, {nx,ny,nz,0}; an invalid record has n = 0
+};
+
+namespace pcp {
+namespace {
+
+constexpr int kPB = 256;
+constexpr int kPAcc = PCP_ICP_PLANE_ACC;
+constexpr int kPBlocks = 2048;  // grid cap of the grid-stride kernels (pcp_icp_accumulate_owned's)
+constexpr uint64_t kNoKey = 0x7fffffffffffffffull;
+constexpr double kMinPivot = 1e-10;
+
+__device__ __forceinline__ bool plane_valid(float nx, float ny, float nz) {
+    return nx * nx + ny * ny + nz * nz >= 0.25f;  // false for a NaN
+}
+
+// one record per target point at its caller index; counts[block] = valid records it wrote
+__global__ void __launch_bounds__(kPB) k_planes_build(const float* xyz, size_t ts, const float* nrm, size_t ns,
+                                                      int64_t n, float4* rec, uint32_t* counts) {
+    uint32_t cnt = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float* p = xyz + (size_t)i * ts;
+        const float* v = nrm + (size_t)i * ns;
+        float4 a = make_float4(p[0], p[1], p[2], 0.f), b = make_float4(v[0], v[1], v[2], 0.f);
+        const bool fin = isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && isfinite(b.x) && isfinite(b.y) &&
+                         isfinite(b.z);
+        if (fin && plane_valid(b.x, b.y, b.z)) {
+            cnt++;
+        } else {
+            if (!fin) a = make_float4(0.f, 0.f, 0.f, 0.f);
+            b = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        rec[2 * i] = a;
+        rec[2 * i + 1] = b;
+    }
+    __shared__ uint32_t sm[kPB / 64];
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < kPB / 64; w++) t += sm[w];
+        counts[blockIdx.x] = t;
+    }
+}
+
+// Block partials of the 30 accumulators (pcp.h): grid-stride over the queries in their original
+// order, per-lane fp64 sums, one wave reduction, one LDS reduction.  The pose is the device 4x4
+// cast to fp32 and applied by k_acc_owned's fmaf chain; products of widened fp32 values and the
+// differences are plain fp64 operations (no contraction), so negating n negates c and r exactly
+// and every accumulated term is unchanged.
+__global__ void __launch_bounds__(kPB) k_acc_plane(const double* T, const float* q, size_t qs, int64_t n,
+                                                   const uint64_t* keys, const float4* rec, uint64_t nrec,
+                                                   double* partials) {
+    float R[9], t[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) R[3 * r + c] = (float)T[4 * r + c];
+        t[r] = (float)T[4 * r + 3];
+    }
+    double acc[kPAcc];
+#pragma unroll
+    for (int k = 0; k < kPAcc; k++) acc[k] = 0.0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = keys[i];
+        const uint64_t j = key & 0xffffffffull;
+        if (key == kNoKey || j >= nrec) continue;
+        const float4 pn = rec[2 * j + 1];
+        if (!plane_valid(pn.x, pn.y, pn.z)) continue;
+        const float4 pp = rec[2 * j];
+        const float* qp = q + (size_t)i * qs;
+        const float x = __fmaf_rn(R[2], qp[2], __fmaf_rn(R[1], qp[1], __fmaf_rn(R[0], qp[0], t[0])));
+        const float y = __fmaf_rn(R[5], qp[2], __fmaf_rn(R[4], qp[1], __fmaf_rn(R[3], qp[0], t[1])));
+        const float z = __fmaf_rn(R[8], qp[2], __fmaf_rn(R[7], qp[1], __fmaf_rn(R[6], qp[0], t[2])));
+        const double qx = x, qy = y, qz = z, nx = pn.x, ny = pn.y, nz = pn.z;
+        double J[6];
+        J[0] = qy * nz - qz * ny;
+        J[1] = qz * nx - qx * nz;
+        J[2] = qx * ny - qy * nx;
+        J[3] = nx; J[4] = ny; J[5] = nz;
+        const double r = (nx * (qx - (double)pp.x) + ny * (qy - (double)pp.y)) + nz * (qz - (double)pp.z);
+        acc[0] += 1.0;
+        int k = 1;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = a; b < 6; b++) acc[k++] += J[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; a++) acc[22 + a] += r * J[a];
+        acc[28] += r * r;
+        acc[29] += (double)__uint_as_float((uint32_t)(key >> 32));
+    }
+    __shared__ double sm[kPB / 64][kPAcc];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kPAcc; k++) {
+        double v = acc[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) sm[wv][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kPAcc) {
+        double v = 0.0;
+        for (int w = 0; w < kPB / 64; w++) v += sm[w][threadIdx.x];
+        partials[(int64_t)blockIdx.x * kPAcc + threadIdx.x] = v;
+    }
+}
+
+// one block: out[k] = sum over the nb block partials, in a fixed order (out may be LDS)
+__device__ void sum_partials(const double* part, int nb, double* out) {
+    __shared__ double s[kPB];
+    for (int k = 0; k < kPAcc; k++) {
+        double v = 0.0;
+        for (int b = threadIdx.x; b < nb; b += kPB) v += part[(int64_t)b * kPAcc + k];
+        s[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = kPB / 2; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[k] = s[0];
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kPB) k_plane_sum(const double* part, int nb, double* out) {
+    sum_partials(part, nb, out);
+}
+
+// The 6x6 solve of pcp.h.  x = (omega, t) minimises sum (r + J . x)^2: A x = -b.  The rotation
+// unknowns are scaled by the RMS lever arm s so that both 3x3 diagonal blocks have the same
+// trace, the system is divided by its largest diagonal entry, and the pivots of the unpivoted
+// LDL^T of that unit-scale matrix decide: <= 1e-10 is numerically singular (a plane's three
+// free motions, two planes' one), and thin but determined systems stay well above it.
+__host__ __device__ int plane_solve(const double acc[kPAcc], double dT[16]) {
+    for (int i = 0; i < 16; i++) dT[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    if (!(acc[0] >= 6.0)) return PCP_ERR_ICP;
+    double A[6][6], rhs[6];
+    int k = 1;
+    for (int a = 0; a < 6; a++)
+        for (int b = a; b < 6; b++) {
+            A[a][b] = acc[k];
+            A[b][a] = acc[k++];
+        }
+    const double tw = A[0][0] + A[1][1] + A[2][2], tt = A[3][3] + A[4][4] + A[5][5];
+    if (!(tt > 0.0) || !(tw > 0.0)) return PCP_ERR_ICP;  // tw == 0: every rotation pivot would be 0
+    const double s = sqrt(tw / tt);
+    double D[6];
+    for (int a = 0; a < 6; a++) D[a] = a < 3 ? 1.0 / s : 1.0;
+    double m = 0.0;
+    for (int a = 0; a < 6; a++) {
+        for (int b = 0; b < 6; b++) A[a][b] = D[a] * A[a][b] * D[b];
+        rhs[a] = -(D[a] * acc[22 + a]);
+        if (A[a][a] > m) m = A[a][a];
+    }
+    if (!(m > 0.0) || !(m < INFINITY)) return PCP_ERR_ICP;
+    for (int a = 0; a < 6; a++) {
+        for (int b = 0; b < 6; b++) A[a][b] /= m;
+        rhs[a] /= m;
+    }
+    double L[6][6], d[6];
+    for (int j = 0; j < 6; j++) {
+        double v = A[j][j];
+        for (int c = 0; c < j; c++) v -= L[j][c] * L[j][c] * d[c];
+        if (!(v > kMinPivot)) return PCP_ERR_ICP;
+        d[j] = v;
+        for (int i = j + 1; i < 6; i++) {
+            double w = A[i][j];
+            for (int c = 0; c < j; c++) w -= L[i][c] * L[j][c] * d[c];
+            L[i][j] = w / v;
+        }
+    }
+    double y[6];
+    for (int i = 0; i < 6; i++) {  // L z = rhs
+        double v = rhs[i];
+        for (int c = 0; c < i; c++) v -= L[i][c] * y[c];
+        y[i] = v;
+    }
+    for (int i = 0; i < 6; i++) y[i] /= d[i];
+    for (int i = 5; i >= 0; i--) {  // L^T y = z / d
+        double v = y[i];
+        for (int c = i + 1; c < 6; c++) v -= L[c][i] * y[c];
+        y[i] = v;
+    }
+    const double w[3] = {D[0] * y[0], D[1] * y[1], D[2] * y[2]};
+    for (int i = 0; i < 6; i++)
+        if (!(fabs(y[i]) < INFINITY)) return PCP_ERR_ICP;  // non-finite accumulators
+    // R = exp([w]x) = I + a K + b K^2, a = sin(th)/th, b = (1 - cos th)/th^2 = (sin(th/2)/(th/2))^2 / 2
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
+    double ca, cb;
+    if (th < 1e-4) {
+        ca = 1.0 - th2 / 6.0 + th2 * th2 / 120.0;
+        cb = 0.5 - th2 / 24.0 + th2 * th2 / 720.0;
+    } else {
+        const double h = sin(0.5 * th) / (0.5 * th);
+        ca = sin(th) / th;
+        cb = 0.5 * h * h;
+    }
+    const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) {
+            double k2 = 0.0;
+            for (int c = 0; c < 3; c++) k2 += K[i][c] * K[c][j];
+            dT[4 * i + j] = (i == j ? 1.0 : 0.0) + ca * K[i][j] + cb * k2;
+        }
+        dT[4 * i + 3] = y[3 + i];
+    }
+    return PCP_OK;
+}
+
+// one thread: solve, T <- dT * T, stats as in pcp.h.  A failed solve latches stats[0] = -1 and
+// freezes T, as k_icp_solve_dev does.
+__device__ void solve_apply(const double* a, double* T, double* stats) {
+    if (stats[0] < 0) return;
+    double dT[16], Tn[16];
+    if (plane_solve(a, dT) != PCP_OK) {
+        stats[0] = -1.0;
+        return;
+    }
+    stats[1] = sqrt(a[29] / a[0]);
+    stats[2] = sqrt(a[28] / a[0]);
+    stats[3] += 1.0;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double v = 0;
+            for (int c = 0; c < 4; c++) v += dT[4 * i + c] * T[4 * c + j];
+            Tn[4 * i + j] = v;
+        }
+    for (int c = 0; c < 16; c++) T[c] = Tn[c];
+}
+
+__global__ void k_plane_solve_dev(const double* acc, double* T, double* stats) {
+    double a[kPAcc];
+    for (int k = 0; k < kPAcc; k++) a[k] = acc[k];
+    solve_apply(a, T, stats);
+}
+
+// the loop's tail in one single-block launch: reduce the block partials, then thread 0 solves
+__global__ void __launch_bounds__(kPB) k_plane_sum_solve(const double* part, int nb, double* T, double* stats) {
+    __shared__ double acc[kPAcc];
+    sum_partials(part, nb, acc);  // ends with a barrier: acc is visible to thread 0
+    if (threadIdx.x == 0) {
+        double a[kPAcc];
+        for (int k = 0; k < kPAcc; k++) a[k] = acc[k];
+        solve_apply(a, T, stats);
+    }
+}
+
+int acc_blocks(int64_t nq) { return (int)std::min<int64_t>(std::max<int64_t>(1, (nq + kPB - 1) / kPB), kPBlocks); }
+
+int check_stride(pcp_ctx* ctx, size_t* stride) {
+    if (*stride == 0) *stride = 3 * sizeof(float);
+    if (*stride % sizeof(float) || *stride < 3 * sizeof(float))
+        return set_error(ctx, PCP_ERR_ARG, "strides must be whole floats, at least 3");
+    return PCP_OK;
+}
+
+void launch_acc(pcp_ctx* ctx, const double* T_dev, const float* q, size_t q_stride, int64_t nq, const uint64_t* keys,
+                const pcp_icp_planes* pl, int nb, double* part) {
+    hipLaunchKernelGGL(k_acc_plane, dim3(nb), dim3(kPB), 0, ctx->stream, T_dev, q, q_stride / sizeof(float), nq, keys,
+                       (const float4*)pl->rec, (uint64_t)pl->n, part);
+}
+
+}  // namespace
+}  // namespace pcp
+
+using namespace pcp;
+
+extern "C" {
+
+int pcp_icp_planes_create(pcp_ctx* ctx, const float* xyz, size_t t_stride, const float* nrm, size_t n_stride,
+                          int64_t n, pcp_icp_planes** out) {
+    if (!ctx || !out || n < 0 || (n > 0 && (!xyz || !nrm))) return PCP_ERR_ARG;
+    *out = nullptr;
+    if (n >= (int64_t)1 << 31) return set_error(ctx, PCP_ERR_ARG, "plane table supports < 2^31 points");
+    PCP_TRY(check_stride(ctx, &t_stride));
+    PCP_TRY(check_stride(ctx, &n_stride));
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    Tmp tmp(ctx);
+    float4* rec = nullptr;
+    uint32_t* counts = nullptr;
+    PCP_TRY(tmp.get(&rec, 2 * (size_t)n));
+    const int nb = acc_blocks(n);
+    PCP_TRY(tmp.get(&counts, (size_t)nb));
+    hipLaunchKernelGGL(k_planes_build, dim3(nb), dim3(kPB), 0, ctx->stream, xyz, t_stride / sizeof(float), nrm,
+                       n_stride / sizeof(float), n, rec, counts);
+    PCP_LAUNCH_CHECK(ctx);
+    std::vector<uint32_t> h((size_t)nb);
+    PCP_HIP(ctx, hipMemcpyAsync(h.data(), counts, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pcp_icp_planes* pl = new pcp_icp_planes();
+    pl->owner = ctx;
+    ctx_retain(ctx);
+    pl->n = n;
+    for (uint32_t c : h) pl->valid += c;
+    pl->rec = tmp.release(rec);
+    *out = pl;
+    return PCP_OK;
+}
+
+int pcp_icp_planes_destroy(pcp_icp_planes* pl) {
+    if (!pl) return PCP_ERR_ARG;
+    if (pl->owner) (void)hipSetDevice(pl->owner->device);
+    dfree(pl->owner, pl->rec);
+    pcp_ctx* owner = pl->owner;
+    delete pl;
+    ctx_release(owner);
+    return PCP_OK;
+}
+
+int64_t pcp_icp_planes_size(const pcp_icp_planes* pl) { return pl ? pl->n : -1; }
+int64_t pcp_icp_planes_valid(const pcp_icp_planes* pl) { return pl ? pl->valid : -1; }
+
+int pcp_icp_accumulate_plane(pcp_ctx* ctx, const double* T_dev, const float* q_dev, size_t q_stride, int64_t nq,
+                             const uint64_t* keys_dev, const pcp_icp_planes* planes, double* acc_dev) {
+    if (!ctx || !T_dev || nq < 0 || (nq > 0 && (!q_dev || !keys_dev)) || !planes || !acc_dev) return PCP_ERR_ARG;
+    PCP_TRY(check_stride(ctx, &q_stride));
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    const int nb = acc_blocks(nq);
+    Tmp tmp(ctx);
+    double* part = nullptr;
+    PCP_TRY(tmp.get(&part, (size_t)nb * kPAcc));
+    launch_acc(ctx, T_dev, q_dev, q_stride, nq, keys_dev, planes, nb, part);
+    hipLaunchKernelGGL(k_plane_sum, dim3(1), dim3(kPB), 0, ctx->stream, (const double*)part, nb, acc_dev);
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
+int pcp_icp_solve_plane(const double acc[30], double dT[16]) {
+    if (!acc || !dT) return PCP_ERR_ARG;
+    return plane_solve(acc, dT);
+}
+
+int pcp_icp_solve_plane_dev(pcp_ctx* ctx, const double* acc_dev, double* T_dev, double* stats_dev) {
+    if (!ctx || !acc_dev || !T_dev || !stats_dev) return PCP_ERR_ARG;
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_plane_solve_dev, dim3(1), dim3(1), 0, ctx->stream, acc_dev, T_dev, stats_dev);
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
+int pcp_icp_run_plane_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
+                          size_t q_stride, int64_t nq, double* T_dev, float rmax, int iters, double* stats_dev) {
+    if (!ctx || !icp || !planes || nq < 0 || (nq > 0 && !q_dev) || !T_dev || !stats_dev || iters < 0 ||
+        !(rmax >= 0.f))
+        return PCP_ERR_ARG;
+    PCP_TRY(check_stride(ctx, &q_stride));
+    if (nq != icp_query_count(icp))
+        return set_error(ctx, PCP_ERR_ARG, "pcp_icp_run_plane_dev: nq = %lld, the handle has %lld queries", (long long)nq,
+                         (long long)icp_query_count(icp));
+    if (planes->n != icp_target(icp)->n_in)
+        return set_error(ctx, PCP_ERR_ARG, "pcp_icp_run_plane_dev: %lld plane records for a target of %lld points",
+                         (long long)planes->n, (long long)icp_target(icp)->n_in);
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    const int nb = acc_blocks(nq);
+    Tmp tmp(ctx);
+    uint64_t* keys = nullptr;
+    double* part = nullptr;
+    PCP_TRY(tmp.get(&keys, (size_t)nq));
+    PCP_TRY(tmp.get(&part, (size_t)nb * kPAcc));
+    for (int it = 0; it < iters; it++) {
+        if (nq > 0) PCP_TRY(pcp_icp_keys_dev(ctx, icp, T_dev, rmax, 0, keys));
+        launch_acc(ctx, T_dev, q_dev, q_stride, nq, keys, planes, nb, part);
+        hipLaunchKernelGGL(k_plane_sum_solve, dim3(1), dim3(kPB), 0, ctx->stream, (const double*)part, nb, T_dev,
+                           stats_dev);
+    }
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
+}  // extern "C"

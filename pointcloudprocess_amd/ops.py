@@ -413,6 +413,23 @@ class ICP:
         ctx.check(ctx.lib.pcp_icp_run_dev(ctx.h, self.h, _ptr(T_dev), float(rmax), int(iters), int(do_scale),
                                           _ptr(stats)))
 
+    # ---- point-to-plane loop (pcp.h I2: the build's own contract, not trimesh2's)
+    def solve_plane_dev(self, acc, T_dev, stats):
+        """Device 6x6 solve of the 30 plane accumulators: T_dev <- dT * T_dev, stats =
+        [status, RMS point distance, RMS plane distance, iterations solved]."""
+        ctx = self.ctx
+        assert acc.dtype == torch.float64 and acc.numel() >= 30
+        ctx.check(ctx.lib.pcp_icp_solve_plane_dev(ctx.h, _ptr(acc), _ptr(T_dev), _ptr(stats)))
+
+    def run_plane_dev(self, planes, q, T_dev, stats, rmax, iters):
+        """iters x (keys_dev, icp_accumulate_plane, solve_plane_dev) with no host round trip; q:
+        the handle's queries in their original order (n x 3 fp32)."""
+        ctx = self.ctx
+        n = q.shape[0]
+        ctx.check(ctx.lib.pcp_icp_run_plane_dev(ctx.h, self.h, planes.h, _ptr(q) if n else None,
+                                                q.stride(0) * q.element_size(), n, _ptr(T_dev), float(rmax),
+                                                int(iters), _ptr(stats)))
+
     def kernel_ms(self):
         """(ms, launches) of the device-loop correspondence kernels since the last call."""
         ms, n = C.c_double(), C.c_int()
@@ -513,6 +530,61 @@ def icp_solve(acc, do_scale=False):
     return rc, np.array(dT[:]).reshape(4, 4)
 
 
+class IcpPlanes:
+    """pcp_icp_planes: the packed {point, normal} table of an ICP target, one 32-byte record per
+    target point at its caller index.  target_xyz: (n, >= 3) fp32; normals: (n, 3) fp32 or the
+    (n, 6) rows of normals_knn."""
+
+    def __init__(self, ctx, target_xyz, normals):
+        self.ctx = ctx
+        n = target_xyz.shape[0]
+        assert target_xyz.dtype == torch.float32 and normals.dtype == torch.float32 and normals.shape[0] == n
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pcp_icp_planes_create(ctx.h, _ptr(target_xyz) if n else None,
+                                                target_xyz.stride(0) * target_xyz.element_size(),
+                                                _ptr(normals) if n else None,
+                                                normals.stride(0) * normals.element_size(), n, C.byref(h)))
+        self.h = h
+
+    @property
+    def size(self):
+        return self.ctx.lib.pcp_icp_planes_size(self.h)
+
+    @property
+    def valid(self):
+        """Records with a usable normal (|n|^2 >= 0.25, finite point and normal)."""
+        return self.ctx.lib.pcp_icp_planes_valid(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pcp_icp_planes_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def icp_accumulate_plane(ctx, T_dev, q, keys, planes, acc=None):
+    """The 30 point-to-plane accumulators of the queries q (n x 3 fp32, original order) under the
+    device pose T_dev, paired by their keys (ICP.keys_dev) with the records of `planes`."""
+    acc = torch.zeros(30, dtype=torch.float64, device=ctx.device) if acc is None else acc
+    n = q.shape[0]
+    assert keys.numel() >= n and keys.dtype in (torch.int64, torch.uint64) and acc.numel() >= 30
+    ctx.check(ctx.lib.pcp_icp_accumulate_plane(ctx.h, _ptr(T_dev), _ptr(q) if n else None,
+                                               q.stride(0) * q.element_size(), n, _ptr(keys) if n else None,
+                                               planes.h, _ptr(acc)))
+    return acc
+
+
+def icp_solve_plane(acc):
+    """Host 6x6 solve of 30 plane accumulators: (rc, dT); rc = -6 (PCP_ERR_ICP) and the identity
+    for a numerically singular system."""
+    a = np.asarray(acc, dtype=np.float64).reshape(30)
+    dT = (C.c_double * 16)()
+    rc = _lib.load().pcp_icp_solve_plane(_lib.f64arr(a), dT)
+    return rc, np.array(dT[:]).reshape(4, 4)
+
+
 def get_rot_icp(ctx, src, temp, rmax, iters=20, do_scale=False, cell_size=0.0, src_dense=True,
                 temp_dense=True):
     M = (C.c_double * 16)()
@@ -520,4 +592,16 @@ def get_rot_icp(ctx, src, temp, rmax, iters=20, do_scale=False, cell_size=0.0, s
     ctx.check(ctx.lib.pcp_get_rot_icp(ctx.h, _ptr(src), src.shape[0], int(src_dense), _ptr(temp),
                                       temp.shape[0], int(temp_dense), M, float(rmax), int(iters),
                                       int(do_scale), float(cell_size), C.byref(err)))
+    return float(err.value), np.array(M[:]).reshape(4, 4)
+
+
+def get_rot_icp_plane(ctx, src, temp, rmax, iters=4, normals_k=16, cell_size=0.0, src_dense=True,
+                      temp_dense=True):
+    """get_rot_icp with the point-to-plane loop over normals_knn(normals_k) of src: (err, M);
+    err = RMS point distance of the last iteration's pairs, -1 when the solve failed."""
+    M = (C.c_double * 16)()
+    err = C.c_float()
+    ctx.check(ctx.lib.pcp_get_rot_icp_plane(ctx.h, _ptr(src), src.shape[0], int(src_dense), _ptr(temp),
+                                            temp.shape[0], int(temp_dense), M, float(rmax), int(iters),
+                                            int(normals_k), float(cell_size), C.byref(err)))
     return float(err.value), np.array(M[:]).reshape(4, 4)
