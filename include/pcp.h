@@ -507,7 +507,16 @@ int pcp_pose_loop_closure(double* ori_host, const uint64_t* ori_stamps_host, int
  * out_dev NULL = count only.
  * pcp_grid_match: get_grid_cloud(src, src_out, dst, dis) (:160-216): src points with a grid
  * point of their cell within Chebyshev `dis` (cells spanning < 1.5 m in z skipped) and those
- * grid points once each, in the reference's push order; cap >= pcp_grid_size suffices. */
+ * grid points once each, in the reference's push order; cap >= pcp_grid_size suffices.
+ * pcp_grid_last_dedupe: which path the last pcp_grid_add_cloud's de-duplication took: out[0] =
+ * cells whose sub-cell hash filled up (> 3/4 of its slots), so the rest of the cell was tested
+ * by a brute scan of its kept points; out[1] = new arrivals tested by that scan.  Both 0 after
+ * an add of 0 points.  Results do not depend on the path; tests use this to know it ran.
+ *
+ * Non-finite input: a point with non-finite or out-of-int-range x or y goes to the cell the
+ * x86-64 reference binary puts it in, INT_MIN on that axis ((int) of such a value is undefined
+ * in C++; cvttsd2si answers INT_MIN).  NaN z is an ordinary kept point: never a duplicate,
+ * ignored by the z range, and it passes the Chebyshev test on z. */
 typedef struct pcp_grid pcp_grid;
 int pcp_grid_create(pcp_ctx* ctx, pcp_grid** out);
 int pcp_grid_destroy(pcp_grid* grid);
@@ -515,6 +524,7 @@ int pcp_grid_clear(pcp_ctx* ctx, pcp_grid* grid);
 int pcp_grid_add_cloud(pcp_ctx* ctx, pcp_grid* grid, const void* cloud_dev, int64_t n);
 int64_t pcp_grid_size(const pcp_grid* grid);
 int64_t pcp_grid_cells(const pcp_grid* grid);
+int pcp_grid_last_dedupe(const pcp_grid* grid, int64_t out[2]);
 int pcp_grid_points(pcp_ctx* ctx, const pcp_grid* grid, void* out_dev, int64_t cap, int64_t* n_out);
 int pcp_grid_box(pcp_ctx* ctx, const pcp_grid* grid, int i0, int i1, int j0, int j1, void* out_dev, int64_t cap,
                  int64_t* n_out);

@@ -9,6 +9,7 @@
 #include "pcp_oracle.h"
 
 #include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1122,6 +1123,11 @@ static uint64_t g_key(int ix, int iy) {
     return ((uint64_t)((uint32_t)ix ^ 0x80000000u) << 32) | (uint64_t)((uint32_t)iy ^ 0x80000000u);
 }
 static uint32_t g_hash(uint64_t k) { return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 32); }
+/* `int irow = x` as the x86-64 reference binary computes it (cvttsd2si): toward zero, and INT_MIN
+ * for NaN, +-inf and everything outside int, where the C conversion is undefined. */
+static int trunc_x86(double v) {
+    return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
+}
 
 ora_grid* ora_grid_create(void) {
     ora_grid* g = (ora_grid*)calloc(1, sizeof(ora_grid));
@@ -1174,7 +1180,7 @@ static float g_dis2(const ora_point48* a, const ora_point48* b) {
 void ora_grid_add_cloud(ora_grid* g, const ora_point48* in, int n) {
     const double X = 0.04, X2 = X * X;  /* MAX_DIS_2POINT_X, MAX_DIS_2POINT (cloud_grid.cpp:11-12) */
     for (int i = 0; i < n; i++) {
-        const int irow = (int)in[i].x, icol = (int)in[i].y;
+        const int irow = trunc_x86(in[i].x), icol = trunc_x86(in[i].y);
         const uint64_t k = g_key(irow, icol);
         const int c = g_find(g, k);
         if (c < 0) {
@@ -1246,13 +1252,14 @@ int ora_grid_match(const ora_grid* g, const ora_point48* src, int nsrc, float di
     unsigned char** used = (unsigned char**)calloc(g->ncell ? g->ncell : 1, sizeof(unsigned char*));
     int ns = 0, nd = 0;
     for (int i = 0; i < nsrc; i++) {
-        const int c = g_find(g, g_key((int)src[i].x, (int)src[i].y));
+        const int c = g_find(g, g_key(trunc_x86(src[i].x), trunc_x86(src[i].y)));
         if (c < 0) continue;
         const ora_gcell* cell = &g->cells[c];
         double min_z = DBL_MAX, max_z = DBL_MIN;  /* numeric_limits<double>::min() (:185-186) */
-        for (int k = 0; k < cell->n; k++) {
-            min_z = min_z < cell->p[k].z ? min_z : cell->p[k].z;
-            max_z = max_z > cell->p[k].z ? max_z : cell->p[k].z;
+        for (int k = 0; k < cell->n; k++) {  /* std::min(a, b) = b < a ? b : a: a NaN z changes nothing */
+            const double z = cell->p[k].z;
+            min_z = z < min_z ? z : min_z;
+            max_z = z > max_z ? z : max_z;
         }
         if (max_z - min_z < 1.5) continue;
         int is_find = 0;

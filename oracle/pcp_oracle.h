@@ -183,7 +183,9 @@ float ora_get_rot_icp(const ora_point48* src, int ns, int src_dense, const ora_p
 /* CloudGrid (cloud_grid.cpp): a grid of 1 m cells keyed by ((int)x, (int)y), each holding
  * the points kept by add_cloud_internal's sequential 4 cm de-duplication (:34-78).  The
  * restatement keeps the cells in a hash map (as the reference) and reports them in key order
- * ((int)x, then (int)y) where the reference's order is the hash map's (get_grid_cloud). */
+ * ((int)x, then (int)y) where the reference's order is the hash map's (get_grid_cloud).
+ * (int) of a NaN, an infinity or a value outside int is INT_MIN, as cvttsd2si answers in the
+ * x86-64 reference binary; a NaN z is an ordinary kept point that std::min / std::max ignore. */
 typedef struct ora_grid ora_grid;
 ora_grid* ora_grid_create(void);
 void ora_grid_free(ora_grid* g);

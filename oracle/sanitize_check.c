@@ -142,7 +142,38 @@ static void check_i(int n, int nthreads) {
     free(tgt); free(q); free(a); free(b); free(out); free(so);
 }
 
+/* CloudGrid with non-finite and out-of-int-range coordinates: the cell index of such a point is
+ * INT_MIN on that axis by an explicit rule (trunc_x86), no out-of-range conversion is executed */
+static void check_g(void) {
+    const double xs[] = {5.5, NAN, 5.51, INFINITY, 0.5, -INFINITY, 3e10, 5.5, 3e10 + 0.0078125, -3e10,
+                         -0.5, 5.5, NAN, 2147483648.0, -2147483648.5, 2147483647.5, 5.5, NAN};
+    const double ys[] = {7.5, 7.5, 7.5, 7.5, 7.5, 7.5, 7.5, NAN, 7.5, 7.5, 7.5, 7.5, 7.5, 7.5, 7.2, 7.5, INFINITY, NAN};
+    const double zs[] = {1.0, 0.0, 1.0, 0.5, 1.0, 1.0, 1.5, 1.0, 1.5, 2.0, 3.0, NAN, 0.0, 2.5, 0.0, 0.0, 1.0, NAN};
+    enum { N = sizeof(xs) / sizeof(xs[0]) };
+    ora_point48 c[N];
+    memset(c, 0, sizeof(c));
+    for (int i = 0; i < N; i++) {
+        c[i].x = xs[i]; c[i].y = ys[i]; c[i].z = zs[i]; c[i].w = 1.0;
+        c[i].stamp_id = (uint32_t)i;
+    }
+    ora_grid* g = ora_grid_create();
+    ora_grid_add_cloud(g, c, N);
+    ora_point48 out[2 * N], so[N];
+    const int gs = ora_grid_size(g);
+    if (gs != 16) { fprintf(stderr, "check_g: %d kept, 16 expected\n", gs); exit(1); }
+    ora_grid_points(g, out);
+    const int row = ora_grid_box(g, -2147483647 - 1, -2147483647, 7, 8, out);
+    if (row != 8) { fprintf(stderr, "check_g: %d points in cell (INT_MIN, 7), 8 expected\n", row); exit(1); }
+    int nso = 0;
+    ora_grid_match(g, c, N, 0.3f, so, &nso, out);
+    ora_grid_add_cloud(g, c, N);  /* NaN and inf rows are never duplicates: kept again */
+    if (ora_grid_size(g) <= gs || ora_grid_size(g) > 2 * N) { fprintf(stderr, "check_g: second add\n"); exit(1); }
+    ora_grid_points(g, out);
+    ora_grid_free(g);
+}
+
 int main(void) {
+    check_g();
     const int sizes[] = {0, 1, 2, 3, 17, 600, 5000};
     for (size_t s = 0; s < sizeof(sizes) / sizeof(sizes[0]); s++) {
         const int n = sizes[s];

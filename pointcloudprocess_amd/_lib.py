@@ -75,6 +75,7 @@ SIGNATURES = [
     ("pcp_grid_add_cloud", _i32, [_vp, _vp, _vp, _i64]),
     ("pcp_grid_size", _i64, [_vp]),
     ("pcp_grid_cells", _i64, [_vp]),
+    ("pcp_grid_last_dedupe", _i32, [_vp, _P(_i64)]),
     ("pcp_grid_points", _i32, [_vp, _vp, _vp, _i64, _P(_i64)]),
     ("pcp_grid_box", _i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _P(_i64)]),
     ("pcp_grid_match", _i32, [_vp, _vp, _vp, _i64, _f32, _vp, _P(_i64), _vp, _i64, _P(_i64)]),

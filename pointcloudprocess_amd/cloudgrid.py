@@ -49,6 +49,14 @@ class CloudGrid:
     def cells(self):
         return int(self.ctx.lib.pcp_grid_cells(self.h))
 
+    @property
+    def last_dedupe(self):
+        """(cells whose de-duplication switched to the brute scan, new arrivals that scan tested)
+        in the last add_cloud_internal."""
+        out = (C.c_int64 * 2)()
+        self.ctx.check(self.ctx.lib.pcp_grid_last_dedupe(self.h, out))
+        return int(out[0]), int(out[1])
+
     def get_grid_cloud(self):
         n = C.c_int64()
         out = torch.empty((max(self.size, 1), 48), dtype=torch.uint8, device=self.ctx.device)

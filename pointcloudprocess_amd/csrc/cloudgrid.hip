@@ -17,6 +17,14 @@
 //              search), the cell's z-range test, the Chebyshev-dis matches; each grid point is
 //              emitted at its first matching source point (atomicMin), ordered by (that source
 //              index, position) -- the reference's push order.
+//
+// Non-finite input.  `int irow = x` of a NaN, an infinity or a value outside int is undefined in
+// C++; the x86-64 reference binary converts with cvttsd2si, which answers INT_MIN for all of
+// them, and trunc_x86 below does the same explicitly.  So: a point with non-finite or
+// out-of-int-range x or y goes to the cell the x86-64 reference binary puts it in, INT_MIN on
+// that axis.  NaN z is an ordinary kept point: every comparison with it is false, so it is never
+// a duplicate, it does not move a cell's z range (std::min / std::max keep their first argument)
+// and it passes the Chebyshev test on z.
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -31,6 +39,7 @@ struct pcp_grid {
     uint8_t* pts = nullptr;      // n records (48 B), grouped by cell, kept order within a cell
     uint64_t* keys = nullptr;    // ncell cell keys, ascending
     int64_t* cstart = nullptr;   // ncell + 1 offsets into pts
+    int64_t dedupe[2] = {0, 0};  // last add: cells that switched to the brute scan, arrivals it tested
 };
 
 namespace pcp {
@@ -44,6 +53,11 @@ constexpr int kHashSlots = 2048;              // per wave (LDS): sub-cell key + 
 __device__ __forceinline__ uint64_t cell_key(int ix, int iy) {
     return ((uint64_t)((uint32_t)ix ^ 0x80000000u) << 32) | (uint64_t)((uint32_t)iy ^ 0x80000000u);
 }
+// (int)v as the x86-64 reference binary computes it (cvttsd2si): toward zero, and INT_MIN for
+// NaN, +-inf and everything outside int -- written out, no out-of-range conversion is executed
+__device__ __forceinline__ int trunc_x86(double v) {
+    return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
+}
 __device__ __forceinline__ const double* rec_xyz(const uint8_t* base, int64_t i) {
     return (const double*)(base + 48 * i);
 }
@@ -55,7 +69,7 @@ __global__ void k_grid_keys(const uint8_t* old_pts, int64_t n_old, const uint8_t
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < m; t += (int64_t)gridDim.x * blockDim.x) {
         const double* p = t < n_old ? rec_xyz(old_pts, t) : rec_xyz(cloud, t - n_old);
         // int irow = x; int icol = y (truncation toward zero, cloud_grid.cpp:38-39)
-        key[t] = cell_key((int)p[0], (int)p[1]);
+        key[t] = cell_key(trunc_x86(p[0]), trunc_x86(p[1]));
         order[t] = (uint32_t)t;
     }
 }
@@ -87,8 +101,16 @@ __global__ void k_grid_cells(const uint64_t* key, const uint32_t* head_scan, con
         }
 }
 
+// The sub-cell only narrows the search for a conflict; is_dup decides.  Its conversion clamps
+// (NaN -> 0) instead of following trunc_x86: a point with a non-finite coordinate can never be a
+// duplicate, so only its cell matters, and for finite coordinates beyond int's range clamping is
+// monotone, so two points within one sub-cell of each other stay within one clamped sub-cell.
+__device__ __forceinline__ int sub_idx(double v) {
+    const double f = floor(v / kSub);
+    return f >= 2147483647.0 ? INT_MAX : (f <= -2147483648.0 ? INT_MIN : (f == f ? (int)f : 0));
+}
 __device__ __forceinline__ uint32_t sub_key(const double* p) {
-    const int sx = (int)floor(p[0] / kSub), sy = (int)floor(p[1] / kSub), sz = (int)floor(p[2] / kSub);
+    const int sx = sub_idx(p[0]), sy = sub_idx(p[1]), sz = sub_idx(p[2]);
     return ((uint32_t)sx & 0x3ffu) | (((uint32_t)sy & 0x3ffu) << 10) | (((uint32_t)sz & 0xfffu) << 20);
 }
 __device__ __forceinline__ uint32_t sub_key_off(uint32_t k, int dx, int dy, int dz) {
@@ -110,7 +132,7 @@ __device__ __forceinline__ bool is_dup(const double* a, const double* b) {
 // one wave per cell: the reference's sequential arrival loop (cloud_grid.cpp:36-77)
 __global__ __launch_bounds__(64) void k_grid_dedupe(const uint8_t* rec, const int64_t* cstart, int64_t ncell,
                                                     int64_t n_old_total, const uint32_t* order, int32_t* next,
-                                                    int32_t* klist, uint32_t* keep) {
+                                                    int32_t* klist, uint32_t* keep, unsigned long long* stat) {
     __shared__ uint32_t s_key[kHashSlots];
     __shared__ int32_t s_head[kHashSlots];
     const int lane = threadIdx.x;
@@ -125,6 +147,7 @@ __global__ __launch_bounds__(64) void k_grid_dedupe(const uint8_t* rec, const in
         int nfill = 0;         // occupied hash slots
         bool brute = false;    // the hash filled up: scan the kept list instead
         int64_t kc = 0;        // kept so far (klist[s .. s + kc))
+        int64_t nscan = 0;     // new arrivals tested by the brute scan (pcp_grid_last_dedupe)
         for (int64_t t = s; t < e; t++) {
             const double* p = rec_xyz(rec, t);
             const bool old = order[t] < (uint32_t)n_old_total;
@@ -140,6 +163,7 @@ __global__ __launch_bounds__(64) void k_grid_dedupe(const uint8_t* rec, const in
                             dup = is_dup(rec_xyz(rec, q), p);
                     }
                 } else {
+                    nscan++;
                     for (int64_t q = lane; q < kc && !dup; q += 64) dup = is_dup(rec_xyz(rec, klist[s + q]), p);
                 }
                 dup = __ballot(dup) != 0;
@@ -168,6 +192,10 @@ __global__ __launch_bounds__(64) void k_grid_dedupe(const uint8_t* rec, const in
             } else if (lane == 0) {
                 keep[t] = 0u;
             }
+        }
+        if (brute && lane == 0) {
+            atomicAdd(stat, 1ull);
+            atomicAdd(stat + 1, (unsigned long long)nscan);
         }
         __syncthreads();
     }
@@ -246,7 +274,7 @@ __global__ void k_grid_match(const uint8_t* pts, const uint64_t* keys, const int
                              uint32_t* first) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nsrc; i += (int64_t)gridDim.x * blockDim.x) {
         const double* p = rec_xyz(src, i);
-        const uint64_t k = cell_key((int)p[0], (int)p[1]);
+        const uint64_t k = cell_key(trunc_x86(p[0]), trunc_x86(p[1]));
         const int64_t c = lower_bound_u64(keys, ncell, k);
         uint32_t f = 0;
         if (c < ncell && keys[c] == k && tall[c]) {
@@ -321,6 +349,12 @@ int pcp_grid_destroy(pcp_grid* g) {
 
 int64_t pcp_grid_size(const pcp_grid* g) { return g ? g->n : -1; }
 int64_t pcp_grid_cells(const pcp_grid* g) { return g ? g->ncell : -1; }
+int pcp_grid_last_dedupe(const pcp_grid* g, int64_t out[2]) {
+    if (!g || !out) return PCP_ERR_ARG;
+    out[0] = g->dedupe[0];
+    out[1] = g->dedupe[1];
+    return PCP_OK;
+}
 int pcp_grid_points(pcp_ctx* ctx, const pcp_grid* g, void* out_dev, int64_t cap, int64_t* n_out) {
     if (!ctx || !g || !n_out) return PCP_ERR_ARG;
     *n_out = g->n;
@@ -333,6 +367,7 @@ int pcp_grid_points(pcp_ctx* ctx, const pcp_grid* g, void* out_dev, int64_t cap,
 int pcp_grid_add_cloud(pcp_ctx* ctx, pcp_grid* g, const void* cloud_dev, int64_t n) {
     if (!ctx || !g || n < 0 || (n > 0 && !cloud_dev)) return PCP_ERR_ARG;
     if (g->n + n >= ((int64_t)1 << 31)) return set_error(ctx, PCP_ERR_CAPACITY, "CloudGrid: < 2^31 points");
+    g->dedupe[0] = g->dedupe[1] = 0;
     if (n == 0) return PCP_OK;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -370,8 +405,12 @@ int pcp_grid_add_cloud(pcp_ctx* ctx, pcp_grid* g, const void* cloud_dev, int64_t
     PCP_TRY(tmp.get(&next, m));
     PCP_TRY(tmp.get(&klist, m));
     PCP_TRY(tmp.get(&keep, m + 1));
+    unsigned long long* stat;
+    unsigned long long stat_host[2] = {0, 0};
+    PCP_TRY(tmp.get(&stat, 2));
+    PCP_HIP(ctx, hipMemsetAsync(stat, 0, 2 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_grid_dedupe, dim3(grid_for(ncell, 1, 1 << 18)), dim3(64), 0, st, rec, cst, (int64_t)ncell,
-                       g->n, o1, next, klist, keep);
+                       g->n, o1, next, klist, keep, stat);
     // compaction: kept records and the new cell starts
     PCP_HIP(ctx, hipMemcpyAsync(head, keep, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     uint32_t nkeep = 0;
@@ -384,6 +423,7 @@ int pcp_grid_add_cloud(pcp_ctx* ctx, pcp_grid* g, const void* cloud_dev, int64_t
     hipLaunchKernelGGL(k_grid_restart, dim3(grid_for(ncell + 1, 256)), dim3(256), 0, st, cst, head, (int64_t)ncell, m,
                        nkeep, cstart);
     PCP_LAUNCH_CHECK(ctx);
+    PCP_HIP(ctx, hipMemcpyAsync(stat_host, stat, sizeof(stat_host), hipMemcpyDeviceToHost, st));
     PCP_HIP(ctx, hipStreamSynchronize(st));
     tmp.release(pts);
     tmp.release(ckey);
@@ -396,6 +436,8 @@ int pcp_grid_add_cloud(pcp_ctx* ctx, pcp_grid* g, const void* cloud_dev, int64_t
     g->cstart = cstart;
     g->n = nkeep;
     g->ncell = ncell;
+    g->dedupe[0] = (int64_t)stat_host[0];
+    g->dedupe[1] = (int64_t)stat_host[1];
     return PCP_OK;
 }
 
