@@ -136,7 +136,7 @@ struct IcpArgs {
     int ring_all;       // ring kernel: process every query (sparse grid) instead of the list
     int dbg;            // ablation flags (pcp_icp_set_options; profiling only)
     int oct_g;          // octant pass lanes per query: 1, 2, 4, 8, or 0 = by the list's density
-    int ring_g;         // fallback pass lanes per query: 1, 2, 4, 8, or 0 = PCP_RING_G / by length
+    int ring_g;         // fallback pass lanes per query: 1, 2, 4, 8, or 0 = by the list's length
     const float* pose;  // device poses (current, previous: 24 floats) overriding R/t, Rp/tq, or null
     const uint32_t* launch_dev;  // device copy of `launch` (k_pose_set), so a captured launch graph replays
 };
@@ -201,9 +201,6 @@ __device__ __forceinline__ void xform_prev(const IcpArgs& a, const float4 q, flo
 #ifndef PCP_SCAN_UNROLL
 #define PCP_SCAN_UNROLL 4
 #endif
-#ifndef PCP_TRACK_BEST
-#define PCP_TRACK_BEST 0
-#endif
 // the contract's fp32 d2: fmaf(dz,dz,fmaf(dy,dy,dx*dx))
 __device__ __forceinline__ float icp_d2(float qx, float qy, float qz, const float4 p) {
     const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
@@ -228,7 +225,7 @@ struct Best {
     float bd;
     int bj;
     uint32_t bk;
-    float px, py, pz;  // filled by fetch() once the scan is over (or tracked, PCP_TRACK_BEST)
+    float px, py, pz;  // filled by fetch() once the scan is over
     __device__ __forceinline__ void consider(float qx, float qy, float qz, const float4 p, uint32_t k) {
         const float d2 = icp_d2(qx, qy, qz, p);
         const int id = __float_as_int(p.w);
@@ -237,11 +234,6 @@ struct Best {
         bd = take ? d2 : bd;
         bj = take ? id : bj;
         bk = take ? k : bk;
-#if PCP_TRACK_BEST
-        px = take ? p.x : px;
-        py = take ? p.y : py;
-        pz = take ? p.z : pz;
-#endif
     }
     // candidates [s, e) of `pts` (LDS or global); loads issued 4 at a time so the memory
     // latency of a candidate is not serialised behind the previous update
@@ -340,18 +332,10 @@ struct Best {
             const float od = __shfl_xor(bd, s, 64);
             const int oj = __shfl_xor(bj, s, 64);
             const uint32_t ok = (uint32_t)__shfl_xor((int)bk, s, 64);
-#if PCP_TRACK_BEST
-            const float ox = __shfl_xor(px, s, 64), oy = __shfl_xor(py, s, 64), oz = __shfl_xor(pz, s, 64);
-#endif
             const bool t = od < bd || (od == bd && oj < bj);
             bd = t ? od : bd;
             bj = t ? oj : bj;
             bk = t ? ok : bk;
-#if PCP_TRACK_BEST
-            px = t ? ox : px;
-            py = t ? oy : py;
-            pz = t ? oz : pz;
-#endif
         }
     }
     template <typename P>
@@ -435,32 +419,13 @@ __device__ __forceinline__ int wave_max_i(int v) {
 // provisional octant winner (a valid upper bound for the exact fallback search) and go to
 // the wave's fallback segment (ballot + mbcnt, no atomics).
 // Accumulators: per chunk, fp32 products centred on the chunk's first query are summed
-// across the wave with DPP adds (no LDS permutes), un-centred in fp64 by one lane and kept
-// in LDS -- no accumulator registers, so the kernel fits 8 waves per SIMD.
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWMASK, 0xf, false);
-    return v + __int_as_float(t);
-}
-// full-wave fp32 sum (every lane must be active); the total ends in lane 63
-__device__ __forceinline__ float wave_sum_f32(float v) {
-    v = dpp_add<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v = dpp_add<0x141, 0xf>(v);  // row_half_mirror
-    v = dpp_add<0x140, 0xf>(v);  // row_mirror
-    v = dpp_add<0x142, 0xa>(v);  // row_bcast:15
-    v = dpp_add<0x143, 0xc>(v);  // row_bcast:31
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
+// across the wave (wave_acc.hpp), un-centred in fp64 and kept in LDS -- no accumulator
+// registers, so the kernel fits 8 waves per SIMD.
 
 // Add one chunk's accepted pairs (lanes with ok) to the wave's fp64 accumulators S (LDS):
 // fp32 products centred on lane 0's query, summed across the wave and un-centred in fp64
-// (wave_acc.hpp: reduce-scatter butterfly, one lane per accumulator; PCP_WAVE_ACC=0 keeps
-// the former 23 DPP reductions with lane 0 un-centring).  Every lane of the wave must call
-// it (full EXEC).
-#ifndef PCP_WAVE_ACC
-#define PCP_WAVE_ACC 1
-#endif
+// (wave_acc.hpp: reduce-scatter butterfly, one lane per accumulator).  Every lane of the wave
+// must call it (full EXEC).
 __device__ __forceinline__ void chunk_accumulate(bool ok, float qx, float qy, float qz, const Best& b,
                                                  double* S, int lane) {
     if (!__ballot(ok)) return;
@@ -469,34 +434,10 @@ __device__ __forceinline__ void chunk_accumulate(bool ok, float qx, float qy, fl
     const float ccz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qz), 0));
     const float x0 = ok ? qx - ccx : 0.f, x1 = ok ? qy - ccy : 0.f, x2 = ok ? qz - ccz : 0.f;
     const float p0 = ok ? b.px - ccx : 0.f, p1 = ok ? b.py - ccy : 0.f, p2 = ok ? b.pz - ccz : 0.f;
-#if PCP_WAVE_ACC
     const float v[23] = {ok ? 1.f : 0.f, x0, x1, x2, p0, p1, p2,
                          x0 * p0, x0 * p1, x0 * p2, x1 * p0, x1 * p1, x1 * p2, x2 * p0, x2 * p1, x2 * p2,
                          x0 * x0, x0 * x1, x0 * x2, x1 * x1, x1 * x2, x2 * x2, ok ? b.bd : 0.f};
     wave_accumulate(v, S, lane, ccx, ccy, ccz);
-#else
-    const float nn = wave_sum_f32(ok ? 1.f : 0.f);
-    const float A0 = wave_sum_f32(x0), A1 = wave_sum_f32(x1), A2 = wave_sum_f32(x2);
-    const float B0 = wave_sum_f32(p0), B1 = wave_sum_f32(p1), B2 = wave_sum_f32(p2);
-    const float AB[9] = {wave_sum_f32(x0 * p0), wave_sum_f32(x0 * p1), wave_sum_f32(x0 * p2),
-                         wave_sum_f32(x1 * p0), wave_sum_f32(x1 * p1), wave_sum_f32(x1 * p2),
-                         wave_sum_f32(x2 * p0), wave_sum_f32(x2 * p1), wave_sum_f32(x2 * p2)};
-    const float AA[6] = {wave_sum_f32(x0 * x0), wave_sum_f32(x0 * x1), wave_sum_f32(x0 * x2),
-                         wave_sum_f32(x1 * x1), wave_sum_f32(x1 * x2), wave_sum_f32(x2 * x2)};
-    const float DD = wave_sum_f32(ok ? b.bd : 0.f);
-    if (lane == 0) {  // un-centre in fp64: q = a + c, p = b + c
-        const double n = nn, C[3] = {ccx, ccy, ccz}, A[3] = {A0, A1, A2}, B[3] = {B0, B1, B2};
-        S[0] += n;
-        for (int k = 0; k < 3; k++) { S[1 + k] += A[k] + n * C[k]; S[4 + k] += B[k] + n * C[k]; }
-        for (int r = 0; r < 3; r++)
-            for (int k = 0; k < 3; k++)
-                S[7 + 3 * r + k] += (double)AB[3 * r + k] + A[r] * C[k] + C[r] * B[k] + n * C[r] * C[k];
-        const int ir[6] = {0, 0, 0, 1, 1, 2}, ik[6] = {0, 1, 2, 1, 2, 2};
-        for (int m = 0; m < 6; m++)
-            S[16 + m] += (double)AA[m] + A[ir[m]] * C[ik[m]] + C[ir[m]] * A[ik[m]] + n * C[ir[m]] * C[ik[m]];
-        S[22] += DD;
-    }
-#endif
 }
 
 // XCD-blocked work split: workgroups are dealt round-robin over the 8 XCDs, so workgroup b
@@ -531,21 +472,13 @@ __device__ __forceinline__ void write_wave_partials(double (*s_acc)[kAcc], doubl
 
 // Per-lane accumulation: each lane sums its accepted pairs in fp32, centred on the
 // (transformed) first query of the wave's current stretch of chunks, into 23 registers; every
-// kFlush chunks (and at the end) the wave reduces them with DPP adds and lane 0 un-centres the
-// totals in fp64 into the wave's LDS accumulators.  A stretch is at most kFlush * 64
+// kFlush chunks (and at the end) the wave reduces them and un-centres the totals in fp64 into
+// the wave's LDS accumulators (wave_acc.hpp).  A stretch is at most kFlush * 64
 // consecutive sorted queries (a few metres), so the centred fp32 products stay small.
 #ifndef PCP_KFLUSH  // chunks per accumulator stretch
 #define PCP_KFLUSH 32
 #endif
 constexpr int kFlush = PCP_KFLUSH;
-#ifndef PCP_FLUSH_INLINE  // 1: inline the stretch flush (no call frame spilled to scratch)
-#define PCP_FLUSH_INLINE 1
-#endif
-#if PCP_FLUSH_INLINE
-#define PCP_FLUSH_ATTR __attribute__((always_inline))
-#else
-#define PCP_FLUSH_ATTR __attribute__((noinline))
-#endif
 struct LaneAcc {
     float v[kAcc - 1];  // n, A(3), B(3), AB(9), AA(6), D  (centred on c)
     __device__ __forceinline__ void zero() {
@@ -570,28 +503,10 @@ struct LaneAcc {
         v[21] = __fmaf_rn(x[2], x[2], v[21]);
         v[22] += d2;
     }
-    // whole wave (full EXEC): totals -> S (fp64, un-centred by lane 0).  Not inlined: it runs once
-    // per kFlush chunks, and its fp64 temporaries would otherwise raise the loop's register count.
-    __device__ PCP_FLUSH_ATTR void flush(double* S, int lane, float cx, float cy, float cz) {
-#if PCP_WAVE_ACC
+    // whole wave (full EXEC): totals -> S (fp64, un-centred).  Always inlined: as a call, the
+    // stretch flush spilled a 160 B/lane frame to scratch.
+    __device__ __attribute__((always_inline)) void flush(double* S, int lane, float cx, float cy, float cz) {
         wave_accumulate(v, S, lane, cx, cy, cz);
-#else
-        float t[kAcc - 1];
-#pragma unroll
-        for (int k = 0; k < kAcc - 1; k++) t[k] = wave_sum_f32(v[k]);
-        if (lane == 0) {
-            const double n = t[0], C[3] = {cx, cy, cz}, A[3] = {t[1], t[2], t[3]}, B[3] = {t[4], t[5], t[6]};
-            S[0] += n;
-            for (int k = 0; k < 3; k++) { S[1 + k] += A[k] + n * C[k]; S[4 + k] += B[k] + n * C[k]; }
-            for (int r = 0; r < 3; r++)
-                for (int k = 0; k < 3; k++)
-                    S[7 + 3 * r + k] += (double)t[7 + 3 * r + k] + A[r] * C[k] + C[r] * B[k] + n * C[r] * C[k];
-            const int ir[6] = {0, 0, 0, 1, 1, 2}, ik[6] = {0, 1, 2, 1, 2, 2};
-            for (int m = 0; m < 6; m++)
-                S[16 + m] += (double)t[16 + m] + A[ir[m]] * C[ik[m]] + C[ir[m]] * A[ik[m]] + n * C[ir[m]] * C[ik[m]];
-            S[22] += t[22];
-        }
-#endif
         zero();
     }
 };
@@ -1446,10 +1361,7 @@ __global__ void __launch_bounds__(kIcpBlock, MINW) k_icp_octant(IcpArgs a, const
 // (profiles/r02_ring): the short fallback lists of later launches are latency-bound and run
 // ~35 % faster with G = 4, while the long early lists (wide "nothing within rmax" boxes of
 // short rows, whose per-row bookkeeping G lanes would repeat) want one lane per query.
-// PCP_RING_G = 0 picks G on the device from the list's length (ring_lanes), else fixes it.
-#ifndef PCP_RING_G
-#define PCP_RING_G 0
-#endif
+// G is picked on the device from the list's length (ring_lanes) unless IcpArgs::ring_g fixes it.
 __device__ __forceinline__ int ring_lanes(int64_t n, int64_t nq) {
     if (n * 1000 > nq) return 1;
     if (n * 8000 > nq) return 2;
@@ -1561,7 +1473,7 @@ __global__ void __launch_bounds__(kIcpBlock, PCP_RING_WAVES) k_icp_ring(IcpArgs 
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane < kAcc) s_acc[wid][lane] = 0.0;
     const int64_t n = a.ring_all ? a.nq : (int64_t)*list_n;
-    const int G = a.ring_g ? a.ring_g : PCP_RING_G ? PCP_RING_G : (a.ring_all ? 1 : ring_lanes(n, a.nq));  // uniform
+    const int G = a.ring_g ? a.ring_g : (a.ring_all ? 1 : ring_lanes(n, a.nq));  // uniform
     if (G == 1)
         ring_run<1>(a, s_acc, list, list_n);
     else if (G == 2)
@@ -1838,21 +1750,14 @@ __global__ void k_slab_guard(const double* T, double b0, double b1, double b2, d
 }
 
 // ---- query order (pcp_icp_create): queries sorted once by target-grid cell in brick-major
-// order (4x4x4-cell bricks; stable, so input order inside a cell), carried as float4
-// {x, y, z, bits(index)}
-// through the radix sort; non-finite queries get key 64 * nbricks (after every cell) and
+// order (8x8x8-cell bricks, cell order inside a brick -- brick order alone measured 5 % slower
+// searches; stable, so input order inside a cell), carried as float4 {x, y, z, bits(index)}
+// through the radix sort; non-finite queries get key query_key_end (after every cell) and
 // are dropped.
-#ifndef PCP_QKEY_LOCAL  // 0: brick order only (one radix pass less; measured 5 % slower searches)
-#define PCP_QKEY_LOCAL 1
-#endif
-#ifndef PCP_QBRICK  // edge (cells) of the query-order bricks: 4 = the index's bricks
-#define PCP_QBRICK 8
-#endif
-__host__ __device__ inline int64_t qbricks(const GridDesc& g, int a) { return (g.n[a] + PCP_QBRICK - 1) / PCP_QBRICK; }
+constexpr int kQBrick = 8;  // edge (cells) of the query-order bricks (the index's bricks are 4)
+__host__ __device__ inline int64_t qbricks(const GridDesc& g, int a) { return (g.n[a] + kQBrick - 1) / kQBrick; }
 __host__ __device__ inline uint32_t query_key_end(const GridDesc& g) {
-    if (PCP_QBRICK != 4)
-        return (uint32_t)(qbricks(g, 0) * qbricks(g, 1) * qbricks(g, 2) * PCP_QBRICK * PCP_QBRICK * PCP_QBRICK);
-    return (uint32_t)(PCP_QKEY_LOCAL ? g.nbricks * 64 : g.nbricks);
+    return (uint32_t)(qbricks(g, 0) * qbricks(g, 1) * qbricks(g, 2) * kQBrick * kQBrick * kQBrick);
 }
 __global__ void k_query_keys(GridDesc g, const float* q, size_t stride_f, int64_t n, uint32_t* key, float4* rec) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1861,19 +1766,14 @@ __global__ void k_query_keys(GridDesc g, const float* q, size_t stride_f, int64_
         const bool fin = isfinite(x) && isfinite(y) && isfinite(z);
         uint32_t k = query_key_end(g);  // past every brick: non-finite queries sort last
         if (fin) {
-            // the brick (4x4x4 cells) of the octant block origin floor(f - 1/2) the search pass
-            // uses: a 64-query chunk then scans the target rows of about one brick
+            // the brick of the octant block origin floor(f - 1/2) the search pass uses: a
+            // 64-query chunk then scans the target rows of about one brick
             const int cx = clampi((int)floorf(cell_f<float>(g, x, 0) - 0.5f), 0, g.n[0] - 1);
             const int cy = clampi((int)floorf(cell_f<float>(g, y, 1) - 0.5f), 0, g.n[1] - 1);
             const int cz = clampi((int)floorf(cell_f<float>(g, z, 2) - 0.5f), 0, g.n[2] - 1);
-            if (PCP_QBRICK != 4) {
-                constexpr int B = PCP_QBRICK;
-                const int64_t b = ((int64_t)(cz / B) * qbricks(g, 1) + cy / B) * qbricks(g, 0) + cx / B;
-                k = (uint32_t)(b * B * B * B + ((cz % B) * B + cy % B) * B + cx % B);
-            } else {
-                k = PCP_QKEY_LOCAL ? (uint32_t)(brick_of(g, cx, cy, cz) * 64 + local_of(cx, cy, cz))
-                                   : (uint32_t)brick_of(g, cx, cy, cz);
-            }
+            constexpr int B = kQBrick;
+            const int64_t b = ((int64_t)(cz / B) * qbricks(g, 1) + cy / B) * qbricks(g, 0) + cx / B;
+            k = (uint32_t)(b * B * B * B + ((cz % B) * B + cy % B) * B + cx % B);
         }
         key[i] = k;
         rec[i] = make_float4(x, y, z, __int_as_float((int)i));
@@ -2003,10 +1903,7 @@ struct LookAhead {
 #ifndef PCP_LOOK_ALPHA
 #define PCP_LOOK_ALPHA 0.5f
 #endif
-#ifndef PCP_LOOK_R1  // step ratio assumed at launch 1, which has no previous step (0: no look-ahead there)
-#define PCP_LOOK_R1 0.f
-#endif
-constexpr float kLookAlpha = PCP_LOOK_ALPHA, kLookCap = 0.02f, kLookRmax = 0.9f, kLookR1 = PCP_LOOK_R1;
+constexpr float kLookAlpha = PCP_LOOK_ALPHA, kLookCap = 0.02f, kLookRmax = 0.9f;
 __global__ void k_pose_set(const double* T, HostPose hp, LookAhead la, float* pose, float* hist, uint32_t launch) {
     *(uint32_t*)(pose + 24) = launch;
     for (int k = 0; k < 12; k++) pose[12 + k] = pose[k];
@@ -2038,7 +1935,8 @@ __global__ void k_pose_set(const double* T, HostPose hp, LookAhead la, float* po
     }
     const float step = launch > 0 ? (float)sqrt(s2) : 0.f, prev = pose[kPoseStep];
     float beta = 0.f;
-    const float ratio = launch == 1 ? kLookR1 : (prev > 0.f ? step / prev : 0.f);
+    // launch 1 has no previous step, so no ratio and no look-ahead
+    const float ratio = launch == 1 ? 0.f : (prev > 0.f ? step / prev : 0.f);
     if (!la.off && launch > 0 && step > 0.f && ratio > 0.f && ratio < 1.f) {  // (false for a NaN)
         const float r = fminf(ratio, kLookRmax);
         beta = la.alpha * r / (1.f - r);
@@ -2075,6 +1973,32 @@ __global__ void k_icp_solve_dev(const double* acc, int do_scale, double* T, doub
             Tn[4 * i + j] = v;
         }
     for (int k = 0; k < 16; k++) T[k] = Tn[k];
+}
+
+// The five kernels of a dense-grid launch after the first, on `st` (the context's stream, or a
+// stream under graph capture): verify what the candidate caches can settle, concatenate the
+// per-wave search segments, octant search of that list (`oct`), concatenate the fallback segments,
+// exact fallback.  `a` carries oct_g and ring_g; its partials end at the fallback pass's.
+using OctKernel = void (*)(IcpArgs, const int32_t*, const uint32_t*);
+int icp_chain(pcp_icp* icp, hipStream_t st, IcpArgs& a, OctKernel oct) {
+    pcp_ctx* ctx = icp->ctx;
+    uint32_t* const svc_n = icp->sv_off + a.nseg_v;  // the two lists' lengths follow their segments' offsets
+    uint32_t* const fbc_n = icp->fb_off + a.nseg;
+    a.partials = icp->partials;
+    hipLaunchKernelGGL(k_icp_verify, dim3(icp->nb_ver), dim3(kIcpBlock), 0, st, a);
+    hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg_v + 3) / 4)), dim3(256), 0, st,
+                       (const int32_t*)icp->sv, (const uint32_t*)icp->sv_count, a.nseg_v, a.sv_seg, icp->svc, svc_n);
+    if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_ver, st));
+    a.partials += (int64_t)icp->nb_ver * kAcc;
+    hipLaunchKernelGGL(oct, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, st, a, (const int32_t*)icp->svc,
+                       (const uint32_t*)svc_n);
+    if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_mid, st));
+    hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg + 3) / 4)), dim3(256), 0, st,
+                       (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, a.nseg, a.fb_seg, icp->fbc, fbc_n);
+    a.partials += (int64_t)icp->nb_fast * kAcc;
+    hipLaunchKernelGGL(k_icp_ring, dim3(icp->nb_ring), dim3(kIcpBlock), 0, st, a, a.partials,
+                       (const int32_t*)icp->fbc, (const uint32_t*)fbc_n);
+    return PCP_OK;
 }
 
 // T (host) or T_dev (device pose, read by k_pose_from_T) -- exactly one is non-null
@@ -2166,50 +2090,31 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     // long list (measured 1.57 against 1.88 ms on the C4 registration).  A captured graph is
     // replayed at every later launch, so it holds the look-ahead form and starts at launch 2:
     // replayed and plain launches then run the same kernels at every launch.
-    using OctKernel = void (*)(IcpArgs, const int32_t*, const uint32_t*);
     const OctKernel oct_graph =
         icp->no_look ? k_icp_octant<PCP_OCT_WAVES_LIST, false> : k_icp_octant<PCP_OCT_WAVES_LIST, true>;
-    const OctKernel oct_list =
-        kLookR1 == 0.f && icp->launches <= 1 ? k_icp_octant<PCP_OCT_WAVES_LIST, false> : oct_graph;
-    // A device-pose launch after the first is the same five kernels every time (verify, list
-    // concatenation, octant search, list concatenation, fallback) with the same arguments: the
-    // launch index is read from the device (k_pose_set) and the pose was already.  With
-    // PCP_ICP_OPT_GRAPH the section is captured once per handle into a HIP graph and replayed --
-    // one launch instead of five (measured: host enqueue is not what the loop waits for, and the
-    // replayed section ran 0.5 % slower, so it is off by default).
-    if (icp->graph && T_dev && verify && !icp->dbg && !corr_idx && !args_out && !icp->graph_off &&
-        oct_list == oct_graph) {
+    const OctKernel oct_list = icp->launches <= 1 ? k_icp_octant<PCP_OCT_WAVES_LIST, false> : oct_graph;
+    if (verify) {
         a.oct_g = icp->oct_g_list;
         a.ring_g = icp->ring_g;
-        auto section = [&](hipStream_t st) {
-            IcpArgs b = a;
-            b.partials = part_v;
-            hipLaunchKernelGGL(k_icp_verify, dim3(icp->nb_ver), dim3(kIcpBlock), 0, st, b);
-            hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((b.nseg_v + 3) / 4)), dim3(256), 0, st,
-                               (const int32_t*)icp->sv, (const uint32_t*)icp->sv_count, b.nseg_v, b.sv_seg, icp->svc,
-                               icp->sv_off + b.nseg_v);
-            b.partials = part_o;
-            hipLaunchKernelGGL(oct_graph, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, st, b, (const int32_t*)icp->svc,
-                               (const uint32_t*)(icp->sv_off + b.nseg_v));
-            hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((b.nseg + 3) / 4)), dim3(256), 0, st,
-                               (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, b.nseg, b.fb_seg, icp->fbc,
-                               icp->fb_off + b.nseg);
-            b.partials = part_r;
-            hipLaunchKernelGGL(k_icp_ring, dim3(icp->nb_ring), dim3(kIcpBlock), 0, st, b, part_r,
-                               (const int32_t*)icp->fbc, (const uint32_t*)(icp->fb_off + b.nseg));
-        };
-        if (icp->gexec && icp->graph_r2 != a.r2) {  // captured for another rmax (replays are stream-ordered)
+        // A device-pose launch after the first is the same five kernels every time with the same
+        // arguments: the launch index is read from the device (k_pose_set) and the pose was already.
+        // With PCP_ICP_OPT_GRAPH the chain is captured once per handle into a HIP graph and replayed --
+        // one launch instead of five (measured: host enqueue is not what the loop waits for, and the
+        // replayed chain ran 0.5 % slower, so it is off by default).
+        const bool graph = icp->graph && T_dev && !icp->dbg && !corr_idx && !args_out && !icp->graph_off &&
+                           oct_list == oct_graph;
+        if (graph && icp->gexec && icp->graph_r2 != a.r2) {  // captured for another rmax (replays are stream-ordered)
             (void)hipStreamSynchronize(ctx->stream);
             (void)hipGraphExecDestroy(icp->gexec);
             icp->gexec = nullptr;
         }
-        if (!icp->gexec) {  // captured on the context's side stream (capture enqueues nothing)
+        if (graph && !icp->gexec) {  // captured on the context's side stream (capture enqueues nothing)
             hipStream_t cap = nullptr;
             hipError_t e = side_stream(ctx, &cap) == PCP_OK ? hipSuccess : hipErrorInvalidValue;
             hipGraph_t gr = nullptr;
             if (e == hipSuccess) e = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
-                section(cap);
+                (void)icp_chain(icp, cap, a, oct_graph);
                 e = hipStreamEndCapture(cap, &gr);
             }
             if (e == hipSuccess) e = hipGraphInstantiate(&icp->gexec, gr, nullptr, nullptr, 0);
@@ -2221,54 +2126,31 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
             }
             icp->graph_r2 = a.r2;
         }
-        if (icp->gexec) PCP_HIP(ctx, hipGraphLaunch(icp->gexec, ctx->stream));
-        else section(ctx->stream);
-        PCP_HIP(ctx, hipEventRecord(e1, ctx->stream));
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kAcc * kRedGroups), 0, ctx->stream, icp->partials,
-                           icp->nb_ver + icp->nb_fast + icp->nb_ring, acc_dev, (const uint32_t*)(icp->fb_off + a.nseg));
-        icp->launches++;
-        PCP_LAUNCH_CHECK(ctx);
-        return PCP_OK;
-    }
-    if (a.g.dense) {
-        // 1. settle what the candidate caches can; the rest -> search list
-        if (verify) {
-            a.partials = part_v;
-            hipLaunchKernelGGL(k_icp_verify, dim3(icp->nb_ver), dim3(kIcpBlock), 0, ctx->stream, a);
-            hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg_v + 3) / 4)), dim3(256), 0, ctx->stream,
-                               (const int32_t*)icp->sv, (const uint32_t*)icp->sv_count, a.nseg_v, a.sv_seg, icp->svc,
-                               icp->sv_off + a.nseg_v);
-        } else {
-            PCP_HIP(ctx, hipMemsetAsync(part_v, 0, (size_t)icp->nb_ver * kAcc * sizeof(double), ctx->stream));
-        }
-        if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_ver, ctx->stream));
-        // 2. octant search of the list (every query at the first launch); unsettled -> fallback list
-        a.partials = part_o;
-        {
-            const int32_t* lst = verify ? (const int32_t*)icp->svc : nullptr;
-            const uint32_t* lst_n = verify ? (const uint32_t*)(icp->sv_off + a.nseg_v) : nullptr;
-            a.oct_g = verify ? icp->oct_g_list : icp->oct_g_first;
-            if (verify)
-                hipLaunchKernelGGL(oct_list, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, ctx->stream, a, lst, lst_n);
-            else  // every query, beta = 0: the plain form
-                hipLaunchKernelGGL((k_icp_octant<PCP_OCT_WAVES, false>), dim3(icp->nb_fast), dim3(kIcpBlock), 0,
-                                   ctx->stream, a, lst, lst_n);
-        }
+        if (graph && icp->gexec) PCP_HIP(ctx, hipGraphLaunch(icp->gexec, ctx->stream));
+        else PCP_TRY(icp_chain(icp, ctx->stream, a, oct_list));
     } else {
-        PCP_HIP(ctx, hipMemsetAsync(part_v, 0, (size_t)(icp->nb_ver + icp->nb_fast) * kAcc * sizeof(double),
-                                    ctx->stream));
+        // the first launch (nothing cached: the octant search takes every query, beta = 0, the plain
+        // form) or a sparse grid (the fallback pass takes every query)
+        const int nb_idle = a.g.dense ? icp->nb_ver : icp->nb_ver + icp->nb_fast;
+        PCP_HIP(ctx, hipMemsetAsync(part_v, 0, (size_t)nb_idle * kAcc * sizeof(double), ctx->stream));
+        if (a.g.dense) {
+            if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_ver, ctx->stream));
+            a.partials = part_o;
+            a.oct_g = icp->oct_g_first;
+            hipLaunchKernelGGL((k_icp_octant<PCP_OCT_WAVES, false>), dim3(icp->nb_fast), dim3(kIcpBlock), 0,
+                               ctx->stream, a, (const int32_t*)nullptr, (const uint32_t*)nullptr);
+        }
+        if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_mid, ctx->stream));
+        if (a.g.dense) {  // compact the per-wave fallback segments into one list
+            hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg + 3) / 4)), dim3(256), 0, ctx->stream,
+                               (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, a.nseg, a.fb_seg, icp->fbc,
+                               icp->fb_off + a.nseg);
+        }
+        a.partials = part_r;
+        a.ring_g = icp->ring_g;
+        hipLaunchKernelGGL(k_icp_ring, dim3(icp->nb_ring), dim3(kIcpBlock), 0, ctx->stream, a, part_r,
+                           (const int32_t*)icp->fbc, (const uint32_t*)(icp->fb_off + a.nseg));
     }
-    if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_mid, ctx->stream));
-    if (a.g.dense) {  // compact the per-wave fallback segments into one list
-        hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg + 3) / 4)), dim3(256), 0, ctx->stream,
-                           (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, a.nseg, a.fb_seg, icp->fbc,
-                           icp->fb_off + a.nseg);
-    }
-    // 3. exact fallback (or every query on a sparse grid)
-    a.partials = part_r;
-    a.ring_g = icp->ring_g;
-    hipLaunchKernelGGL(k_icp_ring, dim3(icp->nb_ring), dim3(kIcpBlock), 0, ctx->stream, a, part_r,
-                       (const int32_t*)icp->fbc, (const uint32_t*)(icp->fb_off + a.nseg));
     PCP_HIP(ctx, hipEventRecord(e1, ctx->stream));
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kAcc * kRedGroups), 0, ctx->stream, icp->partials,
                        icp->nb_ver + icp->nb_fast + icp->nb_ring, acc_dev,
@@ -2371,7 +2253,7 @@ int icp_check_grid(pcp_ctx* ctx, const GridDesc& g, int64_t n_target, int64_t nq
         return set_error(ctx, rc, rc == PCP_ERR_CAPACITY ? "ICP target must have < 2^28 - 1 points (32-bit record offsets)"
                                                          : "ICP supports < 2^31 queries");
     if (g.nbricks * 64 >= ((int64_t)1 << 32) ||
-        qbricks(g, 0) * qbricks(g, 1) * qbricks(g, 2) * PCP_QBRICK * PCP_QBRICK * PCP_QBRICK >= ((int64_t)1 << 32))
+        qbricks(g, 0) * qbricks(g, 1) * qbricks(g, 2) * kQBrick * kQBrick * kQBrick >= ((int64_t)1 << 32))
         return set_error(ctx, PCP_ERR_UNSUPPORTED, "ICP target grid too large for 32-bit cell keys");
     return PCP_OK;
 }
@@ -2675,9 +2557,11 @@ int pcp_icp_step(pcp_ctx* ctx, pcp_icp* icp, const double T[16], float rmax, dou
     return PCP_OK;
 }
 
-int pcp_icp_keys(pcp_ctx* ctx, pcp_icp* icp, const double T[16], float rmax, int64_t target_offset,
-                 uint64_t* keys_dev) {
-    if (!ctx || !icp || !T || !keys_dev || !(rmax >= 0.f) || target_offset < 0 ||
+// pcp_icp_keys / pcp_icp_keys_dev: one launch for the correspondences only, then their keys.
+// T (host) or T_dev (device pose) -- exactly one is non-null
+static int icp_keys(pcp_ctx* ctx, pcp_icp* icp, const double* T, const double* T_dev, float rmax,
+                    int64_t target_offset, uint64_t* keys_dev) {
+    if (!ctx || !icp || (!T && !T_dev) || !keys_dev || !(rmax >= 0.f) || target_offset < 0 ||
         target_offset + pcp_index_size(icp->target) > ((int64_t)1 << 32))
         return PCP_ERR_ARG;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
@@ -2685,7 +2569,7 @@ int pcp_icp_keys(pcp_ctx* ctx, pcp_icp* icp, const double T[16], float rmax, int
     const int saved = icp->dbg;
     icp->dbg |= pcp::kDbgNoAccum;  // correspondences only
     pcp::IcpArgs a{};
-    const int rc = pcp::icp_launch(icp, T, rmax, icp->acc, nullptr, nullptr, nullptr, &a);
+    const int rc = pcp::icp_launch(icp, T, rmax, icp->acc, nullptr, nullptr, T_dev, &a);
     icp->dbg = saved;
     PCP_TRY(rc);
     if (icp->nq_in > icp->nq)
@@ -2698,27 +2582,14 @@ int pcp_icp_keys(pcp_ctx* ctx, pcp_icp* icp, const double T[16], float rmax, int
     return PCP_OK;
 }
 
+int pcp_icp_keys(pcp_ctx* ctx, pcp_icp* icp, const double T[16], float rmax, int64_t target_offset,
+                 uint64_t* keys_dev) {
+    return icp_keys(ctx, icp, T, nullptr, rmax, target_offset, keys_dev);
+}
+
 int pcp_icp_keys_dev(pcp_ctx* ctx, pcp_icp* icp, const double* T_dev, float rmax, int64_t target_offset,
                      uint64_t* keys_dev) {
-    if (!ctx || !icp || !T_dev || !keys_dev || !(rmax >= 0.f) || target_offset < 0 ||
-        target_offset + pcp_index_size(icp->target) > ((int64_t)1 << 32))
-        return PCP_ERR_ARG;
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    icp->ctx = ctx;
-    const int saved = icp->dbg;
-    icp->dbg |= pcp::kDbgNoAccum;  // correspondences only
-    pcp::IcpArgs a{};
-    const int rc = pcp::icp_launch(icp, nullptr, rmax, icp->acc, nullptr, nullptr, T_dev, &a);
-    icp->dbg = saved;
-    PCP_TRY(rc);
-    if (icp->nq_in > icp->nq)
-        hipLaunchKernelGGL(pcp::k_fill_keys, dim3(pcp::grid_for(icp->nq_in, 256)), dim3(256), 0, ctx->stream, keys_dev,
-                           icp->nq_in);
-    if (icp->nq > 0)
-        hipLaunchKernelGGL(pcp::k_make_keys, dim3(pcp::grid_for(icp->nq, 256)), dim3(256), 0, ctx->stream, a,
-                           (uint32_t)target_offset, keys_dev);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
+    return icp_keys(ctx, icp, nullptr, T_dev, rmax, target_offset, keys_dev);
 }
 
 int pcp_keys_owner(pcp_ctx* ctx, const uint64_t* keys_dev, int64_t n, const int64_t* bounds_dev, int nshards,

@@ -41,20 +41,8 @@ __host__ __device__ inline double cell_margin64(const GridDesc& g) {
 #ifndef PCP_KNN_BATCH
 #define PCP_KNN_BATCH 4
 #endif
-#ifndef PCP_COOP_KTH_BISECT  // far pass: shared bound by counting bisection (1) or the exact k-th merge (0)
-#define PCP_COOP_KTH_BISECT 1
-#endif
-#ifndef PCP_COOP_VISIT_BATCH  // far pass: point loads in flight per visit step
-#define PCP_COOP_VISIT_BATCH 1
-#endif
-#ifndef PCP_TILE_MORTON  // tiled normals: queries in Morton order inside each brick (1) or index order (0)
-#define PCP_TILE_MORTON 1
-#endif
 #ifndef PCP_T_MX  // tiled normals: keys kept per lane beyond k (the re-rank's slack)
 #define PCP_T_MX 1
-#endif
-#ifndef PCP_T_PF  // tiled normals: the next chunk's positions loaded a chunk ahead
-#define PCP_T_PF 1
 #endif
 #ifndef PCP_T_SB  // staged points per lane per load batch (tiled normals)
 #define PCP_T_SB 4
@@ -64,21 +52,6 @@ __host__ __device__ inline double cell_margin64(const GridDesc& g) {
 #endif
 #ifndef PCP_T_WB  // window rows per batch of cell-start loads (tiled normals)
 #define PCP_T_WB 5
-#endif
-#ifndef PCP_TILE_ROWTAB  // tiled normals: per-point row bytes in LDS (1) or binary searches of the row table (0)
-#define PCP_TILE_ROWTAB 1
-#endif
-#ifndef PCP_TILE_LANE_DEFAULT  // tiled normals: each lane scans its own window (1) or the union box (0)
-#define PCP_TILE_LANE_DEFAULT 1
-#endif
-#ifndef PCP_NEAR_ROWS  // normals near pass on dense grids: 1 = row walk of the cell window, 0 = cell rings
-#define PCP_NEAR_ROWS 1
-#endif
-#ifndef PCP_COOP_FLAT  // far pass: 1 = a batch's occupied-brick rows dealt over the lanes
-#define PCP_COOP_FLAT 1
-#endif
-#ifndef PCP_NORMALS_NEAR_DEFAULT  // tiled normals: 1 = the lane-per-query near pass before the far pass
-#define PCP_NORMALS_NEAR_DEFAULT 1
 #endif
 #ifndef PCP_T_NOPCA  // profiling builds only: the tile skips its mean/covariance passes (planes wrong)
 #define PCP_T_NOPCA 0
@@ -201,50 +174,7 @@ struct CoopVisitor {
     __device__ __forceinline__ void take(double d, int j) {
         if (d <= shared * (1.0 + 1e-12)) top.push(d, j);
     }
-    __device__ void visit(uint32_t s, uint32_t e) {
-        constexpr int U = PCP_COOP_VISIT_BATCH;
-        uint32_t t = s;
-        if (U > 1) {
-            for (; t + U <= e; t += U) {
-                double4 p[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) p[u] = pts[t + u];
-#pragma unroll
-                for (int u = 0; u < U; u++) take(l2_simple(qx, qy, qz, p[u]), (int)p[u].w);
-            }
-        }
-        for (; t < e; t++) {
-            const double4 p = pts[t];
-            take(l2_simple(qx, qy, qz, p), (int)p.w);
-        }
-    }
 };
-// the exact k-th (d2, j) of the union of the lanes' lists (wave-uniform; every lane calls):
-// k rounds of a wave-wide lexicographic argmin on a copy of the lists
-template <int K>
-__device__ double global_kth(const TopK<K>& top, int kk, int lane) {
-    TopK<K> c = top;
-    c.normalize(kk);
-    double kth = INFINITY;
-    for (int r = 0; r < kk; r++) {
-        double bd = c.best_d();
-        int bj = c.best_j(), bl = lane;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double od = __shfl_xor(bd, o, 64);
-            const int oj = __shfl_xor(bj, o, 64), ol = __shfl_xor(bl, o, 64);
-            const bool take = lex_less(od, oj, bd, bj);
-            bd = take ? od : bd;
-            bj = take ? oj : bj;
-            bl = take ? ol : bl;
-        }
-        if (bj == INT_MAX) return INFINITY;  // fewer than kk points scanned
-        if (lane == bl) c.pop_best();
-        kth = bd;
-    }
-    return kth;
-}
-
 // An upper bound on the wave's exact k-th d2 within 2^-20 of it, without copying the lists:
 // the smallest tau (a double whose low word is all ones) with at least kk list entries <= tau,
 // by bisection on tau's high word; each step counts the entries with one compare per slot into
@@ -360,7 +290,7 @@ __device__ void coop_search(const GridDesc& g, double mc, CoopVisitor<K>& v, int
     uint32_t rs = 0, rl = 0;  // this lane's pending cell range (flushed every 64 items)
     for (int s = 0; s <= smax + 1; s++) {
         if (s > 0) {
-            v.shared = fmin(v.shared, PCP_COOP_KTH_BISECT ? kth_bound<K>(v.top, kk) : global_kth<K>(v.top, kk, lane));
+            v.shared = fmin(v.shared, kth_bound<K>(v.top, kk));
             const double rmin = (double)(s - 1) + dmin - mc;
             if (rmin > 0 && rmin * rmin * h2 > v.ubound()) return;
         }
@@ -409,18 +339,16 @@ __device__ void coop_search(const GridDesc& g, double mc, CoopVisitor<K>& v, int
     farb = max(farb, max(by - (g.nb[1] - 1), -by));
     farb = max(farb, max(bz - (g.nb[2] - 1), -bz));
     const int sbmax = farb + max(g.nb[0], max(g.nb[1], g.nb[2]));
-#if PCP_COOP_FLAT
     __shared__ int4 s_flat[kB / 64][64 * kCoopBB];  // per wave: a batch's occupied bricks {x, y, z, word}
     __shared__ uint16_t s_rows[kB / 64][64 * kCoopBB * 16];  // per wave: their non-empty rows (brick << 4 | row)
     int4* const flat = s_flat[threadIdx.x >> 6];
     uint16_t* const rows = s_rows[threadIdx.x >> 6];
-#endif
     // rings closer than `farb` lie wholly outside the grid (a query far away from it)
     if (tk) tk[0] = clock64();
     for (int sb = farb; sb <= sbmax; sb++) {
         if (shells) (*shells)++;
         const long long c0 = tk ? (long long)clock64() : 0;
-        v.shared = fmin(v.shared, PCP_COOP_KTH_BISECT ? kth_bound<K>(v.top, kk) : global_kth<K>(v.top, kk, lane));
+        v.shared = fmin(v.shared, kth_bound<K>(v.top, kk));
         if (tk) tk[1] += (long long)clock64() - c0;
         if (sb > 0) {
             const double rmin = (double)(4 * (sb - 1)) + bdmin - mc;
@@ -460,9 +388,7 @@ __device__ void coop_search(const GridDesc& g, double mc, CoopVisitor<K>& v, int
             const int64_t t0 = base + lane;
             int bxs[kBB], bys[kBB], bzs[kBB];
             int32_t occ[kBB];
-#if PCP_COOP_FLAT
             uint32_t msk[kBB], bat[kBB];  // row masks and flat[] positions of this lane's bricks
-#endif
 #pragma unroll
             for (int u = 0; u < kBB; u++) {
                 const int64_t t = t0 + 64 * u;
@@ -489,7 +415,6 @@ __device__ void coop_search(const GridDesc& g, double mc, CoopVisitor<K>& v, int
             }
             const long long cb1 = tk ? (long long)clock64() : 0;
             if (tk) tk[2] += cb1 - cb0;  // brick coordinates, pruning and occupancy loads
-#if PCP_COOP_FLAT
             // The batch's occupied bricks are listed in LDS, then their rows that hold points
             // (the brick word's row mask on dense fp64 grids; all 16 rows otherwise) as one flat
             // item list dealt round-robin over the lanes: every lane's round is one row's
@@ -573,45 +498,6 @@ __device__ void coop_search(const GridDesc& g, double mc, CoopVisitor<K>& v, int
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next batch rewrites flat[]
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#else
-#pragma unroll 1
-            for (int u = 0; u < kBB; u++) {
-                if (occ[u] < 0) continue;  // empty or pruned brick
-                const int xb = bxs[u], yb = bys[u], zb = bzs[u];
-                // the brick's rows of 4 cells are contiguous point ranges (x fastest, dense or
-                // brick-slot layout): one range per row run instead of one per cell
-                const int xc0 = 4 * xb, xc1 = min(4 * xb + 3, g.n[0] - 1);
-                const int64_t rowbase = g.dense ? 0 : (int64_t)occ[u] * 64;
-                for (int z = 4 * zb; z < min(4 * zb + 4, g.n[2]); z++) {
-                    const double cz2 = sq_gap(axis_gap<double>(z, cz, lz), mc);
-                    const bool zin = abs(z - cz) <= kCellRings;
-                    for (int y = 4 * yb; y < min(4 * yb + 4, g.n[1]); y++) {
-                        const double cyz2 = cz2 + sq_gap(axis_gap<double>(y, cy, ly), mc);
-                        if (cyz2 * h2 > v.bound()) continue;
-                        const bool yzin = zin && abs(y - cy) <= kCellRings;
-                        // cells within the bound form an interval around cx; phase 1's cells
-                        // (|x - cx| <= kCellRings on this row) are cut out of it
-                        int xa = xc0, xe = xc1;
-                        while (xa <= xe && (cyz2 + sq_gap(axis_gap<double>(xa, cx, lx), mc)) * h2 > v.bound()) xa++;
-                        while (xe >= xa && (cyz2 + sq_gap(axis_gap<double>(xe, cx, lx), mc)) * h2 > v.bound()) xe--;
-                        if (xa > xe) continue;
-                        const int64_t r0 = g.dense ? dense_id(g, 0, y, z) : rowbase + local_of(0, y, z);
-                        auto run = [&](int x0, int x1) {  // cells [x0, x1] of this row
-                            if (x0 > x1) return;
-                            const int64_t c0 = g.dense ? r0 + x0 : r0 + (x0 & 3);
-                            const uint32_t st = g.cstart[c0], en = g.cstart[c0 + (x1 - x0) + 1];
-                            if (en > st) v.visit(st, en);
-                        };
-                        if (yzin) {
-                            run(xa, min(xe, cx - kCellRings - 1));
-                            run(max(xa, cx + kCellRings + 1), xe);
-                        } else {
-                            run(xa, xe);
-                        }
-                    }
-                }
-            }
-#endif
             const long long cb2 = tk ? (long long)clock64() : 0;
             if (tk) tk[3] += cb2 - cb1;  // the occupied bricks' rows and points
             // tighten the shared bound mid-shell (the exact k-th is refreshed per shell)
@@ -1150,32 +1036,23 @@ template <int K>
 __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double4* pts, const int32_t* mapping,
                                                      int identity, int64_t n, int kk, int R, double mc,
                                                      pcp_plane* out, int64_t n_out, FarList far,
-                                                     unsigned long long* stats, const uint32_t* order,
-                                                     int lane_mode) {
+                                                     unsigned long long* stats, const uint32_t* order) {
     constexpr int M = K + PCP_T_MX;
     constexpr uint32_t kMax = 0xffffffffu;
     __shared__ uint2 s_u[kTileCap];
     __shared__ uint32_t s_rs[kTileRows], s_rb[kTileRows + 1];
-#if PCP_TILE_ROWTAB
     __shared__ uint8_t s_row[kTileCap];  // the (y, z) row of each staged point
-#endif
     const int lane = threadIdx.x;
-#if PCP_T_PF
     // the next chunk's sorted positions are loaded a chunk ahead (the chain order -> point ->
     // cells -> rows -> staging starts one round trip shorter)
     uint32_t s_next = blockIdx.x * 64 < n ? order[min((int64_t)blockIdx.x * 64 + lane, n - 1)] : 0u;
-#endif
     for (int64_t c = blockIdx.x; c * 64 < n; c += gridDim.x) {
         const bool valid = c * 64 + lane < n;
-#if PCP_T_PF
         const int64_t s = s_next;  // a sorted position
         {
             const int64_t cn = c + gridDim.x;
             if (cn * 64 < n) s_next = order[min(cn * 64 + lane, n - 1)];
         }
-#else
-        const int64_t s = order[valid ? c * 64 + lane : c * 64];  // a sorted position
-#endif
         const double4 q = pts[s];
         const int cx = cell_i<double>(g, q.x, 0), cy = cell_i<double>(g, q.y, 1), cz = cell_i<double>(g, q.z, 2);
         // Groups of lanes, each staged and scanned on its own: the whole wave when its box fits
@@ -1237,17 +1114,6 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
                          oz = g.o[2] + (double)b.z0 * g.h;
             const int ext = max(max(b.x1 - b.x0, b.y1 - b.y0), b.z1 - b.z0) + 1;
             const double step = (double)ext * g.h / (double)kTileQ, inv = 1.0 / step;
-#if !PCP_TILE_ROWTAB
-            const int nrow = b.nrow;
-            auto row_of = [&](uint32_t e) {
-                int r = 0;
-#pragma unroll
-                for (int stp = (kTileRows + 1) / 2; stp > 0; stp >>= 1)
-                    r = (r + stp < nrow && s_rb[r + stp] <= e) ? r + stp : r;
-                return r;
-            };
-#endif
-#if PCP_TILE_ROWTAB
             // e advances by 64 per step, so each lane's row only moves forward: a short walk
             // instead of a binary search, and the row of every staged point is kept (one byte)
             // for the re-rank's list index -> position lookups.  kSB entries per lane per step:
@@ -1285,14 +1151,6 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
                                             (uint32_t)quant14(pz[u] - oz, inv));
                 }
             }
-#else
-            for (uint32_t e = lane; e < total; e += 64) {
-                const int r = row_of(e);
-                const double4 p = pts[s_rs[r] + (e - s_rb[r])];
-                s_u[e] = make_uint2((uint32_t)quant14(p.x - ox, inv) | ((uint32_t)quant14(p.y - oy, inv) << 16),
-                                    (uint32_t)quant14(p.z - oz, inv));
-            }
-#endif
             wave_lds_fence();
             const uint32_t qxy = (uint32_t)quant14(q.x - ox, inv) | ((uint32_t)quant14(q.y - oy, inv) << 16);
             const int qz = quant14(q.z - oz, inv);
@@ -1309,7 +1167,7 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
                 for (int i = M; i >= 1; i--) t[i] = umed3_(t[i - 1], t[i], x);
                 t[0] = min(t[0], x);
             };
-            // Per-lane windows (lane_mode, R <= kLaneR): each lane scans only the rows of ITS OWN
+            // Per-lane windows (R <= kLaneR): each lane scans only the rows of ITS OWN
             // (2R+1)^2 (y, z) window -- the x-range of its +-R cells, nearest rows first -- from
             // the staged list, instead of every point of the wave's union box (a compact patch's
             // union box holds 4-10x a lane's window).  The lanes walk their own row lists (kept in
@@ -1321,7 +1179,7 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
             bool lane_path = false;
             const bool act = mine && valid;
             const int wx0 = max(cx - R, b.x0), wx1 = min(cx + R, b.x1);
-            if (lane_mode && R <= kLaneR) {
+            if (R <= kLaneR) {
                 constexpr int kW = (2 * kLaneR + 1) * (2 * kLaneR + 1);
                 const int nwin = R >= 2 ? 25 : (R == 1 ? 9 : 1);
                 // the LDS run [a, e) of every window row as a | e << 16 (0: empty / outside the
@@ -1456,11 +1314,7 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
             for (int i = 0; i < M; i++) {
                 const bool has = t[i] != kMax;
                 const uint32_t ei = t[i] & (uint32_t)(kTileCap - 1);
-#if PCP_TILE_ROWTAB
                 const int r = s_row[has ? ei : 0u];
-#else
-                const int r = row_of(has ? ei : 0u);
-#endif
                 P[i] = has ? s_rs[r] + (ei - s_rb[r]) : 0u;
             }
 #pragma unroll
@@ -1921,8 +1775,7 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
         unsigned bits = 1;
         while (bits < 32 && ((int64_t)1 << bits) < nbr) bits++;
         // Morton bits inside the brick: cell + sub-cell (12) when the key still fits 32 bits
-        int lb = 0;
-        if (PCP_TILE_MORTON) lb = bits + 12 <= 32 ? 12 : (bits + 9 <= 32 ? 9 : 0);
+        const int lb = bits + 12 <= 32 ? 12 : (bits + 9 <= 32 ? 9 : 0);
         hipLaunchKernelGGL(k_brick_keys, dim3(blocks_for(ix->n)), dim3(kB), 0, ctx->stream, ix->g, pts, ix->n, lb, k0,
                            v0);
         bits += (unsigned)lb;
@@ -1930,19 +1783,15 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
         FarBuf fb2;  // the near pass's own deferred queries
         PCP_TRY(fb2.alloc(tmp, ix->n, true));
         // the tile's uncertified queries: the lane-per-query near pass (cell rings), its own
-        // deferrals then the wave-per-query pass (PCP_NORMALS_NEAR_DEFAULT; 0: all of them straight
-        // to the wave-per-query pass, measured slower)
-        const bool near_pass = PCP_NORMALS_NEAR_DEFAULT;
-        const int lane_mode = PCP_TILE_LANE_DEFAULT;  // 0: every lane scans the union box (slower)
+        // deferrals then the wave-per-query pass (all of them straight to the wave-per-query pass
+        // measured slower)
 #define LAUNCH_TILE(KV)                                                                                          \
         hipLaunchKernelGGL((k_normals_tile<KV>), dim3(nbt), dim3(64), 0, ctx->stream, ix->g, pts, ix->mapping,      \
-                           ix->identity, ix->n, kk, tile_R, mc, out, n_out, fb.f, st, order, lane_mode);          \
-        if (near_pass)                                                                                            \
-            hipLaunchKernelGGL((k_normals<KV, false, PCP_NEAR_ROWS != 0>), dim3(blocks_for(ix->n)), dim3(kB), 0,     \
-                               ctx->stream, ix->g,                                                              \
-                               pts, ix->mapping, ix->identity, ix->pos_of_j, ix->n, kk, mc, out, n_out, fb2.f, fb.f); \
+                           ix->identity, ix->n, kk, tile_R, mc, out, n_out, fb.f, st, order);                    \
+        hipLaunchKernelGGL((k_normals<KV, false, true>), dim3(blocks_for(ix->n)), dim3(kB), 0, ctx->stream, ix->g,  \
+                           pts, ix->mapping, ix->identity, ix->pos_of_j, ix->n, kk, mc, out, n_out, fb2.f, fb.f);   \
         hipLaunchKernelGGL((k_normals_coop<KV>), dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts,            \
-                           ix->mapping, ix->identity, ix->pos_of_j, kk, mc, out, n_out, near_pass ? fb2.f : fb.f,  \
+                           ix->mapping, ix->identity, ix->pos_of_j, kk, mc, out, n_out, fb2.f,                     \
                            st ? st + 4 : nullptr)
         switch (K) {
             case 1: case 4: LAUNCH_TILE(4); break;
@@ -1951,8 +1800,8 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
             default: LAUNCH_TILE(32); break;
         }
 #undef LAUNCH_TILE
-        hipLaunchKernelGGL(k_keep_deferred, dim3(1), dim3(1), 0, ctx->stream, fb.f.count,
-                           near_pass ? fb2.f.count : nullptr, ctx->nrm_deferred);
+        hipLaunchKernelGGL(k_keep_deferred, dim3(1), dim3(1), 0, ctx->stream, fb.f.count, fb2.f.count,
+                           ctx->nrm_deferred);
         PCP_LAUNCH_CHECK(ctx);
         ctx->nrm_mode = 1;
 #if PCP_NORMALS_STATS
