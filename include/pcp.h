@@ -475,6 +475,67 @@ int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src_aos48_dev, int64_t ns, i
                           double mat_rot_host[16], float rmax, int iters, int normals_k,
                           double cell_size, float* err);
 
+/* ----------------------------------------------------------------------- I3: trimmed correspondences
+ * A data-driven rejection distance under the build's OWN contract (the reference's maxdist = 0
+ * lets trimesh2 choose one; that library is absent and nothing here restates it): an exact order
+ * statistic of the pairs' squared POINT distances decides which pairs of an iteration are kept.
+ *
+ * pcp_icp_trim_keys, over n keys as pcp_icp_keys* writes them:
+ *   Valid keys.  A key is valid when it is not INT64_MAX.  m is the number of valid keys.
+ *     b_i = key_i >> 32 is an unsigned 32-bit integer.  For the keys pcp_icp_keys* writes, b_i is
+ *     the bit pattern of a finite non-negative fp32 d2; the unsigned order of the b_i is then the
+ *     order of the distances.
+ *   Selection.  r = (uint64) floor((double)frac * (double)(m - 1)), computed on the device in
+ *     fp64.  sel is the r-th smallest b_i, counted from 0 with multiplicity, in unsigned order.
+ *     sel = 0 when m == 0.  The selection is exact: no sampling and no approximate histogram
+ *     answer.
+ *   Cut.  All steps are fp32, round-to-nearest, without contraction: m2 = mult * mult,
+ *     c = m2 * as_float(sel), f2 = d_floor * d_floor, cut = f2 when c is NaN, else max(c, f2)
+ *     (f2 when the two compare equal).
+ *   Keep.  Key i is kept iff it is valid and as_float(b_i) <= cut as a float comparison; a NaN
+ *     pattern is rejected.  keys_out[i] is keys[i] unchanged when kept, including its low 32
+ *     bits; otherwise it is exactly INT64_MAX.  Invalid keys stay INT64_MAX.
+ *   Aliasing.  keys_out_dev == keys_dev (in place) is allowed, and then only the rejected keys
+ *     are stored.  Any other overlap is the caller's error.
+ *   Stats.  trim_dev = {m, kept, sel, bits of cut}, written every call.  n == 0 writes
+ *     {0, 0, 0, bits(f2)} and touches no key.
+ *   Arguments.  PCP_ERR_ARG for: a null context or a null trim_dev; n < 0 or n >= 2^31; null
+ *     key pointers with n > 0; frac outside [0, 1] or NaN; mult or d_floor negative or not
+ *     finite.  These checks read nothing through ctx.
+ *   Execution.  Asynchronous on the context's stream, with no host synchronisation.
+ *     Temporaries come from the per-call guard and are released on return, so
+ *     pcp_ctx_alloc_stats balances, error paths included.  The result is bit-for-bit the same on
+ *     every run: integer histograms and no float atomics.  The keys are read four times (three
+ *     radix-select passes over digits of 11, 11 and 10 bits, and the filter).
+ * The statistic is the POINT distance: on a sparse cloud it is dominated by the sampling spacing,
+ * which is why the rule is a quantile (frac) times a multiplier, not a multiple of the median.
+ *
+ * Trimmed keys compose with everything that reads keys: pcp_icp_accumulate_plane, and for the
+ * point-to-point minimisation pcp_keys_owner (one shard, bounds = {0, n_target}) followed by
+ * pcp_icp_accumulate_owned; all of them skip INT64_MAX.
+ *
+ * pcp_icp_run_plane_trimmed_dev = iters x (pcp_icp_keys_dev at offset 0, pcp_icp_trim_keys in
+ * place, accumulate, solve) on the context's stream with no host round trip.  Arguments and
+ * stats_dev as pcp_icp_run_plane_dev, plus the trim's; trim_dev receives the stats of the last
+ * iteration's trim (untouched when iters == 0).  rmax stays the search bound: the trim only
+ * tightens it.  A trim that leaves fewer than 6 pairs makes the solve fail and freezes T. */
+#define PCP_ICP_TRIM_STATS 4
+int pcp_icp_trim_keys(pcp_ctx* ctx, const uint64_t* keys_dev, int64_t n, float frac, float mult,
+                      float d_floor, uint64_t* keys_out_dev, uint64_t* trim_dev /* 4 */);
+int pcp_icp_run_plane_trimmed_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes,
+                                  const float* q_dev, size_t q_stride_bytes, int64_t nq, double* T_dev,
+                                  float rmax, float frac, float mult, float d_floor, int iters,
+                                  double* stats_dev /* 4 */, uint64_t* trim_dev /* 4: last iteration */);
+/* pcp_get_rot_icp_plane through the trimmed loop: the same steps (joint centroid, centring,
+ * normals, plane table, un-centring), rmax <= 0 -> PCP_ERR_UNSUPPORTED as there, the trim's
+ * argument rules for frac, mult and d_floor.  *kept_out (optional) = the pairs kept by the last
+ * iteration's trim (0 when nothing ran). */
+int pcp_get_rot_icp_plane_trimmed(pcp_ctx* ctx, const void* src_aos48_dev, int64_t ns, int src_is_dense,
+                                  const void* temp_aos48_dev, int64_t nt, int temp_is_dense,
+                                  double mat_rot_host[16], float rmax, float frac, float mult,
+                                  float d_floor, int iters, int normals_k, double cell_size, float* err,
+                                  int64_t* kept_out);
+
 /* ----------------------------------------------------------------------- I4: pose lines
  * Host-only (no device work): n frames' poses as row-major 4x4 doubles, rots[16 * i].
  *

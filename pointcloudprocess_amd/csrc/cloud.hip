@@ -454,17 +454,21 @@ int pcp_get_rot_icp(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, co
 }
 
 // pcp_get_rot_icp's staging (joint centroid, fp32 centring, fp32 target index, query set, the
-// un-centring of t) around the point-to-plane device loop: the build's own contract (pcp.h, I2)
-int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, const void* tmp, int64_t nt,
-                          int tmp_dense, double M[16], float rmax, int iters, int normals_k, double cell_size,
-                          float* err) {
-    if (!ctx || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tmp) || !M || iters < 0)
-        return set_error(ctx, PCP_ERR_ARG, "pcp_get_rot_icp_plane: bad arguments");
+// un-centring of t) around the point-to-plane device loop: the build's own contract (pcp.h, I2).
+// trim = {frac, mult, d_floor} runs the trimmed loop (I3) and reports the pairs its last iteration
+// kept; trim == nullptr is the plain loop.
+static int get_rot_plane(pcp_ctx* ctx, const char* who, const void* src, int64_t ns, int src_dense, const void* tmp,
+                         int64_t nt, int tmp_dense, double M[16], float rmax, const float* trim, int iters,
+                         int normals_k, double cell_size, float* err, int64_t* kept_out) {
+    if (!ctx || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tmp) || !M || iters < 0 ||
+        (trim && !trim_args_ok(trim[0], trim[1], trim[2])))
+        return set_error(ctx, PCP_ERR_ARG, "%s: bad arguments", who);
     if (err) *err = -1.0f;
+    if (kept_out) *kept_out = 0;
     for (int i = 0; i < 16; i++) M[i] = (i % 5 == 0) ? 1.0 : 0.0;
     if (!(rmax > 0.f))
         return set_error(ctx, PCP_ERR_UNSUPPORTED,
-                         "pcp_get_rot_icp_plane: rmax must be > 0 (trimesh2's automatic maxdist = 0 is not provided)");
+                         "%s: rmax must be > 0 (trimesh2's automatic maxdist = 0 is not provided)", who);
     if (ns == 0 || nt == 0) return PCP_OK;  // ICP fails: err < 0
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     double s[4];
@@ -475,11 +479,12 @@ int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src, int64_t ns, int src_den
     float* fs = nullptr;
     float* ft = nullptr;
     pcp_plane* nrm = nullptr;
-    double* pose = nullptr;  // T (16), stats (4)
+    double* pose = nullptr;  // T (16), stats (4), the trimmed loop's trim stats (4 x u64)
+    const size_t npose = trim ? 24 : 20;
     Tmp bufs(ctx);
     PCP_TRY(bufs.get(&fs, 3 * (size_t)ns));
     PCP_TRY(bufs.get(&ft, 3 * (size_t)nt));
-    PCP_TRY(bufs.get(&pose, 20));
+    PCP_TRY(bufs.get(&pose, npose));
     // handles are destroyed on every path, the ICP handle before its target index
     struct Handles {
         pcp_index* ix = nullptr;
@@ -508,10 +513,14 @@ int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src, int64_t ns, int src_den
     h.ix64 = nullptr;
     PCP_TRY(pcp_icp_planes_create(ctx, fs, 3 * sizeof(float), (const float*)nrm, sizeof(pcp_plane), ns, &h.planes));
     bufs.free(nrm);
-    double T[20] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0};
-    PCP_HIP(ctx, hipMemcpyAsync(pose, T, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    PCP_TRY(pcp_icp_run_plane_dev(ctx, h.icp, h.planes, ft, 3 * sizeof(float), nt, pose, rmax, iters, pose + 16));
-    PCP_HIP(ctx, hipMemcpyAsync(T, pose, sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    double T[24] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0};
+    PCP_HIP(ctx, hipMemcpyAsync(pose, T, npose * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (trim)
+        PCP_TRY(pcp_icp_run_plane_trimmed_dev(ctx, h.icp, h.planes, ft, 3 * sizeof(float), nt, pose, rmax, trim[0],
+                                              trim[1], trim[2], iters, pose + 16, (uint64_t*)(pose + 20)));
+    else
+        PCP_TRY(pcp_icp_run_plane_dev(ctx, h.icp, h.planes, ft, 3 * sizeof(float), nt, pose, rmax, iters, pose + 16));
+    PCP_HIP(ctx, hipMemcpyAsync(T, pose, npose * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(M, T, 16 * sizeof(double));
     for (int r = 0; r < 3; r++) {  // t' = (t - R c) + c, as pcp_get_rot_icp
@@ -522,7 +531,27 @@ int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src, int64_t ns, int src_den
     }
     // stats: a failed solve (or no solved iteration) reports err = -1, as pcp_get_rot_icp does
     if (err) *err = (T[16] < 0 || T[19] < 1.0) ? -1.0f : (float)T[17];
+    if (trim && kept_out) {
+        uint64_t st[PCP_ICP_TRIM_STATS];
+        std::memcpy(st, T + 20, sizeof(st));
+        *kept_out = (int64_t)st[1];
+    }
     return PCP_OK;
+}
+
+int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, const void* tmp, int64_t nt,
+                          int tmp_dense, double M[16], float rmax, int iters, int normals_k, double cell_size,
+                          float* err) {
+    return get_rot_plane(ctx, "pcp_get_rot_icp_plane", src, ns, src_dense, tmp, nt, tmp_dense, M, rmax, nullptr, iters,
+                         normals_k, cell_size, err, nullptr);
+}
+
+int pcp_get_rot_icp_plane_trimmed(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, const void* tmp, int64_t nt,
+                                  int tmp_dense, double M[16], float rmax, float frac, float mult, float d_floor,
+                                  int iters, int normals_k, double cell_size, float* err, int64_t* kept_out) {
+    const float trim[3] = {frac, mult, d_floor};
+    return get_rot_plane(ctx, "pcp_get_rot_icp_plane_trimmed", src, ns, src_dense, tmp, nt, tmp_dense, M, rmax, trim,
+                         iters, normals_k, cell_size, err, kept_out);
 }
 
 }  // extern "C"

@@ -157,6 +157,13 @@ int seqfold_aos48(pcp_ctx* ctx, const void* p0, int64_t n0, const void* p1, int6
 const pcp_index* icp_target(const pcp_icp* icp);
 int64_t icp_query_count(const pcp_icp* icp);
 
+// pcp_icp_trim_keys (icp_trim.hip) for callers that have checked the arguments (trim_args_ok and
+// the pointers) and own the work memory (trim_work_bytes, reusable from call to call).
+size_t trim_work_bytes();
+bool trim_args_ok(float frac, float mult, float d_floor);
+int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
+                    uint64_t* out, uint64_t* trim, uint32_t* work);
+
 // Exclusive scan of `n` uint32 values in place (values' total must fit uint32).
 // Returns the total through *total_dev (device, optional) and *total_host (optional, syncs).
 int scan_u32_inplace(pcp_ctx* ctx, uint32_t* data, int64_t n, uint32_t* total_host);

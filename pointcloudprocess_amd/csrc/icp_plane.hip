@@ -2,7 +2,8 @@
 // correspondence search stays in icp.hip; this file takes its per-query winner keys
 // (pcp_icp_keys_dev) and does the minimisation: a packed {point, normal} table of the target,
 // the 30 accumulators of sum (n . (T q - p))^2 linearised at the pose, the scaled 6x6 LDL^T
-// solve, and the device loop around the three.
+// solve, and the device loop around the three (with the trim of icp_trim.hip between the keys and
+// the accumulation in its trimmed form, pcp.h I3).
 //
 // The accumulation's cost is its gather: one 32-byte record per pair at a data-dependent index,
 // both halves in one 64-byte line (two arrays would cost two lines).  Everything else streams.
@@ -280,6 +281,41 @@ void launch_acc(pcp_ctx* ctx, const double* T_dev, const float* q, size_t q_stri
                        (const float4*)pl->rec, (uint64_t)pl->n, part);
 }
 
+// iters x (keys, [trim in place: trim = {frac, mult, d_floor}, stats of the last one to trim_dev,]
+// accumulate, sum + solve) on ctx's stream with no host round trip
+int run_plane_loop(pcp_ctx* ctx, const char* who, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
+                   size_t q_stride, int64_t nq, double* T_dev, float rmax, const float* trim, int iters,
+                   double* stats_dev, uint64_t* trim_dev) {
+    if (!ctx || !icp || !planes || nq < 0 || (nq > 0 && !q_dev) || !T_dev || !stats_dev || iters < 0 ||
+        !(rmax >= 0.f))
+        return PCP_ERR_ARG;
+    PCP_TRY(check_stride(ctx, &q_stride));
+    if (nq != icp_query_count(icp))
+        return set_error(ctx, PCP_ERR_ARG, "%s: nq = %lld, the handle has %lld queries", who, (long long)nq,
+                         (long long)icp_query_count(icp));
+    if (planes->n != icp_target(icp)->n_in)
+        return set_error(ctx, PCP_ERR_ARG, "%s: %lld plane records for a target of %lld points", who,
+                         (long long)planes->n, (long long)icp_target(icp)->n_in);
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    const int nb = acc_blocks(nq);
+    Tmp tmp(ctx);
+    uint64_t* keys = nullptr;
+    double* part = nullptr;
+    uint32_t* work = nullptr;
+    PCP_TRY(tmp.get(&keys, (size_t)nq));
+    PCP_TRY(tmp.get(&part, (size_t)nb * kPAcc));
+    if (trim) PCP_TRY(tmp.get(&work, trim_work_bytes() / sizeof(uint32_t)));
+    for (int it = 0; it < iters; it++) {
+        if (nq > 0) PCP_TRY(pcp_icp_keys_dev(ctx, icp, T_dev, rmax, 0, keys));
+        if (trim) PCP_TRY(trim_keys_async(ctx, keys, nq, trim[0], trim[1], trim[2], keys, trim_dev, work));
+        launch_acc(ctx, T_dev, q_dev, q_stride, nq, keys, planes, nb, part);
+        hipLaunchKernelGGL(k_plane_sum_solve, dim3(1), dim3(kPB), 0, ctx->stream, (const double*)part, nb, T_dev,
+                           stats_dev);
+    }
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
 }  // namespace
 }  // namespace pcp
 
@@ -360,31 +396,17 @@ int pcp_icp_solve_plane_dev(pcp_ctx* ctx, const double* acc_dev, double* T_dev, 
 
 int pcp_icp_run_plane_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
                           size_t q_stride, int64_t nq, double* T_dev, float rmax, int iters, double* stats_dev) {
-    if (!ctx || !icp || !planes || nq < 0 || (nq > 0 && !q_dev) || !T_dev || !stats_dev || iters < 0 ||
-        !(rmax >= 0.f))
-        return PCP_ERR_ARG;
-    PCP_TRY(check_stride(ctx, &q_stride));
-    if (nq != icp_query_count(icp))
-        return set_error(ctx, PCP_ERR_ARG, "pcp_icp_run_plane_dev: nq = %lld, the handle has %lld queries", (long long)nq,
-                         (long long)icp_query_count(icp));
-    if (planes->n != icp_target(icp)->n_in)
-        return set_error(ctx, PCP_ERR_ARG, "pcp_icp_run_plane_dev: %lld plane records for a target of %lld points",
-                         (long long)planes->n, (long long)icp_target(icp)->n_in);
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    const int nb = acc_blocks(nq);
-    Tmp tmp(ctx);
-    uint64_t* keys = nullptr;
-    double* part = nullptr;
-    PCP_TRY(tmp.get(&keys, (size_t)nq));
-    PCP_TRY(tmp.get(&part, (size_t)nb * kPAcc));
-    for (int it = 0; it < iters; it++) {
-        if (nq > 0) PCP_TRY(pcp_icp_keys_dev(ctx, icp, T_dev, rmax, 0, keys));
-        launch_acc(ctx, T_dev, q_dev, q_stride, nq, keys, planes, nb, part);
-        hipLaunchKernelGGL(k_plane_sum_solve, dim3(1), dim3(kPB), 0, ctx->stream, (const double*)part, nb, T_dev,
-                           stats_dev);
-    }
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
+    return run_plane_loop(ctx, "pcp_icp_run_plane_dev", icp, planes, q_dev, q_stride, nq, T_dev, rmax, nullptr, iters,
+                          stats_dev, nullptr);
+}
+
+int pcp_icp_run_plane_trimmed_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
+                                  size_t q_stride, int64_t nq, double* T_dev, float rmax, float frac, float mult,
+                                  float d_floor, int iters, double* stats_dev, uint64_t* trim_dev) {
+    if (!trim_dev || !trim_args_ok(frac, mult, d_floor)) return PCP_ERR_ARG;
+    const float trim[3] = {frac, mult, d_floor};
+    return run_plane_loop(ctx, "pcp_icp_run_plane_trimmed_dev", icp, planes, q_dev, q_stride, nq, T_dev, rmax, trim,
+                          iters, stats_dev, trim_dev);
 }
 
 }  // extern "C"

@@ -1,0 +1,255 @@
+// Trimmed correspondences (include/pcp.h, I3): an exact order statistic of the d2 words of the
+// pcp_icp_keys_dev keys, and a filter that rewrites the keys above the cut derived from it to
+// INT64_MAX, the "no pair" key every accumulator already skips.
+//
+// The selection is a most-significant-digit-first radix select on the high word b = key >> 32,
+// digits of 11 / 11 / 10 bits: three histogram passes over the keys (per-block LDS histograms
+// merged into one global histogram with integer atomics) and, after each, one block that finds
+// the digit holding the wanted rank and the rank left inside it.  The filter is the fourth and
+// last read.  Everything is integer counting, so the result is the same bit for bit on every run.
+//
+// ICP distances sit in a handful of exponents, so in the leading digit almost every lane of a
+// wave lands in the same few bins, and 64 same-address LDS atomics serialise.  Each wave therefore
+// peels up to kPeel groups first: the lanes that share the first active lane's digit are counted
+// with a ballot and added by one lane.  What is still active after kPeel rounds (digits spread
+// over many bins, where collisions are rare) adds one by one.
+#include <algorithm>
+#include <cmath>
+
+#include "common.hpp"
+
+namespace pcp {
+namespace {
+
+constexpr int kTB = 256;
+constexpr int kTPer = 4;             // keys per thread and block iteration of the histogram passes
+constexpr int kTHistBlocks = 1024;   // grid cap of the histogram passes (4 blocks of 8 KB LDS per CU)
+constexpr int kTFilterBlocks = 2048; // grid cap of the filter
+constexpr int kPeel = 4;
+constexpr int kTBins = 2048;         // bins of the widest digit
+constexpr uint64_t kNoKey = 0x7fffffffffffffffull;
+
+__host__ __device__ constexpr int digit_bits(int p) { return p == 2 ? 10 : 11; }
+__host__ __device__ constexpr int digit_shift(int p) { return p == 0 ? 21 : p == 1 ? 10 : 0; }
+
+// work memory: hist[3][kTBins] u32, then the state between the passes
+struct TrimState {
+    uint64_t rank;    // rank left inside the bins chosen so far
+    uint64_t m;       // valid keys
+    uint32_t prefix;  // the digits chosen so far, most significant first
+    uint32_t pad;
+};
+constexpr size_t kStateWord = 3 * (size_t)kTBins;  // u32 offset of the state (8-byte aligned)
+
+__device__ __forceinline__ TrimState* state_of(uint32_t* work) { return (TrimState*)(work + kStateWord); }
+
+// count one key's digit of pass P into the block's LDS histogram (called by whole waves)
+template <int P>
+__device__ __forceinline__ void count_digit(uint32_t* h, uint64_t key, uint32_t prefix) {
+    constexpr int shift = digit_shift(P), bits = digit_bits(P);
+    const uint32_t b = (uint32_t)(key >> 32);
+    bool act = key != kNoKey;
+    if constexpr (P > 0) act = act && (b >> (shift + bits)) == prefix;
+    const uint32_t d = (b >> shift) & ((1u << bits) - 1u);
+    const int lane = threadIdx.x & 63;
+    uint64_t todo = __ballot(act);
+#pragma unroll
+    for (int r = 0; r < kPeel; r++) {
+        if (todo == 0) break;  // wave-uniform
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        const uint32_t dl = (uint32_t)__builtin_amdgcn_readlane((int)d, leader);
+        const bool mine = act && d == dl;
+        const uint64_t same = __ballot(mine);
+        if (lane == leader) atomicAdd(&h[dl], (uint32_t)__popcll(same));
+        if (mine) act = false;
+        todo &= ~same;
+    }
+    if (act) atomicAdd(&h[d], 1u);
+}
+
+// pass P: histogram of digit P over the valid keys whose higher digits equal the state's prefix
+template <int P>
+__global__ void __launch_bounds__(kTB) k_trim_hist(const uint64_t* keys, int64_t n, uint32_t* work) {
+    constexpr int nb = 1 << digit_bits(P);
+    __shared__ uint32_t h[nb];
+    for (int b = threadIdx.x; b < nb; b += kTB) h[b] = 0;
+    const uint32_t prefix = P > 0 ? state_of(work)->prefix : 0u;
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * kTB;
+    // the trip count is the same for every thread of the block, so the ballots see whole waves
+    for (int64_t base = (int64_t)blockIdx.x * kTB; base < n; base += kTPer * stride) {
+        uint64_t k[kTPer];
+#pragma unroll
+        for (int u = 0; u < kTPer; u++) {
+            const int64_t i = base + u * stride + threadIdx.x;
+            k[u] = i < n ? keys[i] : kNoKey;
+        }
+#pragma unroll
+        for (int u = 0; u < kTPer; u++) count_digit<P>(h, k[u], prefix);
+    }
+    __syncthreads();
+    uint32_t* g = work + (size_t)P * kTBins;
+    for (int b = threadIdx.x; b < nb; b += kTB) {
+        const uint32_t c = h[b];
+        if (c) atomicAdd(&g[b], c);
+    }
+}
+
+// one block after pass P: the bin holding the rank, the rank left inside it; after the last pass
+// the cut and the stats (kept = 0, the filter adds to it)
+template <int P>
+__global__ void __launch_bounds__(kTB) k_trim_pick(uint32_t* work, float frac, float mult, float d_floor,
+                                                   uint64_t* trim) {
+    constexpr int bits = digit_bits(P), nb = 1 << bits, per = nb / kTB;
+    __shared__ uint32_t part[kTB];
+    __shared__ uint64_t rank_s, left_s;
+    __shared__ uint32_t old_s, pre_s;
+    const int tid = threadIdx.x;
+    const uint32_t* g = work + (size_t)P * kTBins;
+    TrimState* st = state_of(work);
+    uint32_t c[per], s = 0;
+#pragma unroll
+    for (int j = 0; j < per; j++) {
+        c[j] = g[tid * per + j];
+        s += c[j];  // a bin, and their total m, is < 2^31
+    }
+    part[tid] = s;
+    __syncthreads();
+    for (int o = 1; o < kTB; o <<= 1) {
+        const uint32_t v = tid >= o ? part[tid - o] : 0u;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        uint64_t rank;
+        if (P == 0) {
+            const uint64_t m = part[kTB - 1];
+            st->m = m;
+            rank = m ? (uint64_t)floor((double)frac * (double)(m - 1)) : 0;
+            old_s = 0;
+        } else {
+            rank = st->rank;
+            old_s = st->prefix;
+        }
+        rank_s = left_s = rank;
+        pre_s = old_s << bits;  // m == 0: no bin holds the rank and sel stays 0
+    }
+    __syncthreads();
+    const uint64_t rank = rank_s, excl = part[tid] - s;
+    if (rank >= excl && rank < excl + s) {  // one thread at most
+        uint64_t cum = excl;
+#pragma unroll
+        for (int j = 0; j < per; j++) {
+            if (rank < cum + c[j]) {
+                pre_s = (old_s << bits) | (uint32_t)(tid * per + j);
+                left_s = rank - cum;
+                break;
+            }
+            cum += c[j];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        st->prefix = pre_s;
+        st->rank = left_s;
+        if (P == 2) {
+            const uint32_t sel = pre_s;
+            const float m2 = mult * mult;
+            const float cc = m2 * __uint_as_float(sel);
+            const float f2 = d_floor * d_floor;
+            const float cut = (cc > f2) ? cc : f2;  // f2 when cc is NaN
+            trim[0] = st->m;
+            trim[1] = 0;
+            trim[2] = sel;
+            trim[3] = __float_as_uint(cut);
+        }
+    }
+}
+
+__global__ void k_trim_empty(float d_floor, uint64_t* trim) {
+    trim[0] = trim[1] = trim[2] = 0;
+    trim[3] = __float_as_uint(d_floor * d_floor);
+}
+
+// keep a valid key iff as_float(b) <= cut; in place only the rejected keys are stored
+__global__ void __launch_bounds__(kTB) k_trim_filter(const uint64_t* keys, int64_t n, uint64_t* out, int inplace,
+                                                     uint64_t* trim) {
+    const float cut = __uint_as_float((uint32_t)trim[3]);
+    uint32_t cnt = 0;
+    for (int64_t i = blockIdx.x * (int64_t)kTB + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTB) {
+        const uint64_t key = keys[i];
+        const bool valid = key != kNoKey;
+        const bool keep = valid && __uint_as_float((uint32_t)(key >> 32)) <= cut;
+        cnt += keep ? 1u : 0u;
+        if (inplace) {
+            if (valid && !keep) out[i] = kNoKey;
+        } else {
+            out[i] = keep ? key : kNoKey;
+        }
+    }
+    __shared__ uint32_t sm[kTB / 64];
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < kTB / 64; w++) t += sm[w];
+        if (t) atomicAdd((unsigned long long*)&trim[1], (unsigned long long)t);
+    }
+}
+
+template <int P>
+void launch_pass(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
+                 uint64_t* trim, uint32_t* work) {
+    const unsigned nb = grid_for(n, kTB * kTPer, kTHistBlocks);
+    hipLaunchKernelGGL(k_trim_hist<P>, dim3(nb), dim3(kTB), 0, ctx->stream, keys, n, work);
+    hipLaunchKernelGGL(k_trim_pick<P>, dim3(1), dim3(kTB), 0, ctx->stream, work, frac, mult, d_floor, trim);
+}
+
+}  // namespace
+
+size_t trim_work_bytes() { return kStateWord * sizeof(uint32_t) + sizeof(TrimState); }
+
+bool trim_args_ok(float frac, float mult, float d_floor) {
+    return frac >= 0.f && frac <= 1.f && mult >= 0.f && std::isfinite(mult) && d_floor >= 0.f &&
+           std::isfinite(d_floor);
+}
+
+int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
+                    uint64_t* out, uint64_t* trim, uint32_t* work) {
+    if (n == 0) {
+        hipLaunchKernelGGL(k_trim_empty, dim3(1), dim3(1), 0, ctx->stream, d_floor, trim);
+        PCP_LAUNCH_CHECK(ctx);
+        return PCP_OK;
+    }
+    PCP_HIP(ctx, hipMemsetAsync(work, 0, trim_work_bytes(), ctx->stream));
+    launch_pass<0>(ctx, keys, n, frac, mult, d_floor, trim, work);
+    launch_pass<1>(ctx, keys, n, frac, mult, d_floor, trim, work);
+    launch_pass<2>(ctx, keys, n, frac, mult, d_floor, trim, work);
+    hipLaunchKernelGGL(k_trim_filter, dim3(grid_for(n, kTB, kTFilterBlocks)), dim3(kTB), 0, ctx->stream, keys, n, out,
+                       out == keys ? 1 : 0, trim);
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
+}  // namespace pcp
+
+using namespace pcp;
+
+extern "C" {
+
+// the argument checks read nothing through ctx: a rejected call never touches the context
+int pcp_icp_trim_keys(pcp_ctx* ctx, const uint64_t* keys_dev, int64_t n, float frac, float mult, float d_floor,
+                      uint64_t* keys_out_dev, uint64_t* trim_dev) {
+    if (!ctx || !trim_dev || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!keys_dev || !keys_out_dev)) ||
+        !trim_args_ok(frac, mult, d_floor))
+        return PCP_ERR_ARG;
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    Tmp tmp(ctx);
+    uint32_t* work = nullptr;
+    PCP_TRY(tmp.get(&work, trim_work_bytes() / sizeof(uint32_t)));
+    return trim_keys_async(ctx, keys_dev, n, frac, mult, d_floor, keys_out_dev, trim_dev, work);
+}
+
+}  // extern "C"

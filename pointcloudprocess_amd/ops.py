@@ -430,6 +430,20 @@ class ICP:
                                                 q.stride(0) * q.element_size(), n, _ptr(T_dev), float(rmax),
                                                 int(iters), _ptr(stats)))
 
+    def run_plane_trimmed_dev(self, planes, q, T_dev, stats, rmax, frac, mult=1.0, d_floor=0.0, iters=4, trim=None):
+        """run_plane_dev with icp_trim_keys(frac, mult, d_floor) in place between the keys and the
+        accumulation of every iteration (pcp.h I3).  Returns trim: the last iteration's
+        [m, kept, sel, bits of cut] (int64 device tensor, 4)."""
+        ctx = self.ctx
+        n = q.shape[0]
+        trim = torch.zeros(4, dtype=torch.int64, device=ctx.device) if trim is None else trim
+        assert trim.dtype == torch.int64 and trim.numel() >= 4
+        ctx.check(ctx.lib.pcp_icp_run_plane_trimmed_dev(ctx.h, self.h, planes.h, _ptr(q) if n else None,
+                                                        q.stride(0) * q.element_size(), n, _ptr(T_dev), float(rmax),
+                                                        float(frac), float(mult), float(d_floor), int(iters),
+                                                        _ptr(stats), _ptr(trim)))
+        return trim
+
     def kernel_ms(self):
         """(ms, launches) of the device-loop correspondence kernels since the last call."""
         ms, n = C.c_double(), C.c_int()
@@ -576,6 +590,21 @@ def icp_accumulate_plane(ctx, T_dev, q, keys, planes, acc=None):
     return acc
 
 
+def icp_trim_keys(ctx, keys, frac, mult=1.0, d_floor=0.0, out=None):
+    """Trim correspondence keys (pcp.h I3): keep the valid keys whose fp32 d2 (the high word) is <=
+    max(mult^2 * the frac-quantile of the valid d2, d_floor^2); the others become INT64_MAX.
+    out=None writes a new tensor, out=keys works in place.  Returns (keys_out, trim) with trim =
+    [m, kept, sel, bits of cut] as an int64 device tensor."""
+    n = keys.numel()
+    out = torch.empty_like(keys) if out is None else out
+    assert keys.dtype == torch.int64 and out.dtype == torch.int64 and out.numel() >= n
+    assert keys.is_contiguous() and out.is_contiguous()
+    trim = torch.zeros(4, dtype=torch.int64, device=ctx.device)
+    ctx.check(ctx.lib.pcp_icp_trim_keys(ctx.h, _ptr(keys) if n else None, n, float(frac), float(mult),
+                                        float(d_floor), _ptr(out) if n else None, _ptr(trim)))
+    return out, trim
+
+
 def icp_solve_plane(acc):
     """Host 6x6 solve of 30 plane accumulators: (rc, dT); rc = -6 (PCP_ERR_ICP) and the identity
     for a numerically singular system."""
@@ -605,3 +634,17 @@ def get_rot_icp_plane(ctx, src, temp, rmax, iters=4, normals_k=16, cell_size=0.0
                                             temp.shape[0], int(temp_dense), M, float(rmax), int(iters),
                                             int(normals_k), float(cell_size), C.byref(err)))
     return float(err.value), np.array(M[:]).reshape(4, 4)
+
+
+def get_rot_icp_plane_trimmed(ctx, src, temp, rmax, frac, mult=1.0, d_floor=0.0, iters=4, normals_k=16,
+                              cell_size=0.0, src_dense=True, temp_dense=True):
+    """get_rot_icp_plane through the trimmed loop (pcp.h I3): (err, M, kept); kept = the pairs the
+    last iteration's trim kept."""
+    M = (C.c_double * 16)()
+    err = C.c_float()
+    kept = C.c_int64()
+    ctx.check(ctx.lib.pcp_get_rot_icp_plane_trimmed(ctx.h, _ptr(src), src.shape[0], int(src_dense), _ptr(temp),
+                                                    temp.shape[0], int(temp_dense), M, float(rmax), float(frac),
+                                                    float(mult), float(d_floor), int(iters), int(normals_k),
+                                                    float(cell_size), C.byref(err), C.byref(kept)))
+    return float(err.value), np.array(M[:]).reshape(4, 4), int(kept.value)
