@@ -536,6 +536,72 @@ int pcp_get_rot_icp_plane_trimmed(pcp_ctx* ctx, const void* src_aos48_dev, int64
                                   float d_floor, int iters, int normals_k, double cell_size, float* err,
                                   int64_t* kept_out);
 
+/* ----------------------------------------------------------------------- I3b: trim by plane residual
+ * The same rule as I3 over another statistic: the squared PLANE residual of a pair under the
+ * current pose, the quantity the point-to-plane loop minimises.  For a correct pair it is the
+ * sensor noise whatever the sampling spacing, so an order statistic of it separates clutter a few
+ * decimetres off a surface from good pairs, which the point distance of a sparse cloud cannot.
+ * Again the build's OWN contract.  One more key filter in front of the unchanged
+ * pcp_icp_accumulate_plane, as pcp_icp_trim_keys is.
+ *
+ * pcp_icp_trim_keys_plane, over n keys as pcp_icp_keys* writes them, the n queries q_dev they
+ * belong to (original order, stride 0 = 12), the device pose T_dev and the target's plane table:
+ *   Usable pairs.  Key i is usable iff it is not INT64_MAX, its index j = key & 0xffffffff is < the
+ *     table's size (a larger index is never read), record j is valid by pcp_icp_planes's rule, and
+ *     its statistic rho_i is not NaN.  m is the number of usable pairs.
+ *   Statistic.  q' = R q + t with the pose cast to fp32 and the fp32 fmaf chain of
+ *     pcp_icp_accumulate_plane; p, n and q' widened to fp64;
+ *     r = (nx * (q'x - px) + ny * (q'y - py)) + nz * (q'z - pz) in plain fp64 operations in that
+ *     order, without contraction; rho = (float)(r * r): one fp64 product rounded to nearest fp32.
+ *     +inf is an ordinary value.  b_i is the bit pattern of rho_i, a non-negative fp32, so the
+ *     unsigned order of the b_i is the order of the |r|.
+ *   Selection, cut, keep.  pcp_icp_trim_keys's rules word for word over the b_i of the usable
+ *     pairs: r = (uint64) floor((double)frac * (double)(m - 1)) on the device in fp64; sel = the
+ *     r-th smallest b_i, counted from 0 with multiplicity, exact, 0 when m == 0; m2 = mult * mult,
+ *     c = m2 * as_float(sel), f2 = d_floor * d_floor in fp32, cut = f2 when c is NaN, else
+ *     max(c, f2); pair i is kept iff it is usable and rho_i <= cut.  mult and d_floor therefore act
+ *     on the plane distance |r|.
+ *   Output.  keys_out[i] is keys[i] unchanged when kept, all 64 bits: the high word is still the
+ *     POINT d2, so accumulator [29] and stats[1] of the loop keep their meaning.  Every other key
+ *     is exactly INT64_MAX, the unusable ones pcp_icp_accumulate_plane would have skipped anyway
+ *     included.  Hence pcp_icp_accumulate_plane(keys_out)[0] == kept.
+ *   Invariance.  Negating every normal of the table negates r exactly, so keys_out and trim_dev
+ *     are bit for bit unchanged.
+ *   Aliasing.  keys_out_dev == keys_dev (in place) is allowed, and then only rejected keys are
+ *     stored.  Any other overlap is the caller's error.
+ *   Stats.  trim_dev = {m, kept, sel, bits of cut}, written every call.  n == 0 writes
+ *     {0, 0, 0, bits(f2)} and touches no key.
+ *   Arguments.  PCP_ERR_ARG for: a null context, trim_dev, T_dev or planes; n < 0 or n >= 2^31;
+ *     null key or query pointers with n > 0; frac outside [0, 1] or NaN; mult or d_floor negative
+ *     or not finite; a stride that is not a whole number of floats or is below 12 (0 = 12).  A
+ *     rejected call writes nothing.
+ *   Execution.  Asynchronous on the context's stream, with no host synchronisation; temporaries
+ *     (n residual keys and the select's work memory) come from the per-call guard, so
+ *     pcp_ctx_alloc_stats balances, error paths included; the result is bit-for-bit the same on
+ *     every run.  Three steps: a residual pass that writes (b_i << 32 | low word of the key) for a
+ *     usable pair and INT64_MAX otherwise; pcp_icp_trim_keys's radix select over those residual
+ *     keys; a filter pass that reads residual key i and keeps or rejects key i.
+ *
+ * pcp_icp_run_plane_rtrimmed_dev = iters x (pcp_icp_keys_dev at offset 0, pcp_icp_trim_keys_plane
+ * in place at the iteration's pose, accumulate, solve): the arguments, argument checks and stats of
+ * pcp_icp_run_plane_trimmed_dev.  A trim that leaves fewer than 6 pairs makes the solve fail and
+ * freezes T.
+ * pcp_get_rot_icp_plane_rtrimmed: pcp_get_rot_icp_plane_trimmed through that loop; every argument
+ * and output as there. */
+int pcp_icp_trim_keys_plane(pcp_ctx* ctx, const double* T_dev, const float* q_dev, size_t q_stride_bytes,
+                            int64_t n, const uint64_t* keys_dev, const pcp_icp_planes* planes,
+                            float frac, float mult, float d_floor,
+                            uint64_t* keys_out_dev, uint64_t* trim_dev /* 4 */);
+int pcp_icp_run_plane_rtrimmed_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes,
+                                   const float* q_dev, size_t q_stride_bytes, int64_t nq, double* T_dev,
+                                   float rmax, float frac, float mult, float d_floor, int iters,
+                                   double* stats_dev /* 4 */, uint64_t* trim_dev /* 4: last iteration */);
+int pcp_get_rot_icp_plane_rtrimmed(pcp_ctx* ctx, const void* src_aos48_dev, int64_t ns, int src_is_dense,
+                                   const void* temp_aos48_dev, int64_t nt, int temp_is_dense,
+                                   double mat_rot_host[16], float rmax, float frac, float mult,
+                                   float d_floor, int iters, int normals_k, double cell_size, float* err,
+                                   int64_t* kept_out);
+
 /* ----------------------------------------------------------------------- I4: pose lines
  * Host-only (no device work): n frames' poses as row-major 4x4 doubles, rots[16 * i].
  *

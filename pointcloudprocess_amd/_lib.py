@@ -125,6 +125,11 @@ SIGNATURES = [
                                              _vp, _vp]),
     ("pcp_get_rot_icp_plane_trimmed", _i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _P(_f64), _f32, _f32, _f32,
                                              _f32, _i32, _i32, _f64, _P(_f32), _P(_i64)]),
+    ("pcp_icp_trim_keys_plane", _i32, [_vp, _vp, _vp, _sz, _i64, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
+    ("pcp_icp_run_plane_rtrimmed_dev", _i32, [_vp, _vp, _vp, _vp, _sz, _i64, _vp, _f32, _f32, _f32, _f32, _i32,
+                                              _vp, _vp]),
+    ("pcp_get_rot_icp_plane_rtrimmed", _i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _P(_f64), _f32, _f32, _f32,
+                                              _f32, _i32, _i32, _f64, _P(_f32), _P(_i64)]),
 ]
 
 _lib = None

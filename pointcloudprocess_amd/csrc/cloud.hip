@@ -455,11 +455,11 @@ int pcp_get_rot_icp(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, co
 
 // pcp_get_rot_icp's staging (joint centroid, fp32 centring, fp32 target index, query set, the
 // un-centring of t) around the point-to-plane device loop: the build's own contract (pcp.h, I2).
-// trim = {frac, mult, d_floor} runs the trimmed loop (I3) and reports the pairs its last iteration
-// kept; trim == nullptr is the plain loop.
+// trim = {frac, mult, d_floor} runs the trimmed loop (I3; by_plane: the loop that trims by the plane
+// residual, I3b) and reports the pairs its last iteration kept; trim == nullptr is the plain loop.
 static int get_rot_plane(pcp_ctx* ctx, const char* who, const void* src, int64_t ns, int src_dense, const void* tmp,
-                         int64_t nt, int tmp_dense, double M[16], float rmax, const float* trim, int iters,
-                         int normals_k, double cell_size, float* err, int64_t* kept_out) {
+                         int64_t nt, int tmp_dense, double M[16], float rmax, const float* trim, bool by_plane,
+                         int iters, int normals_k, double cell_size, float* err, int64_t* kept_out) {
     if (!ctx || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tmp) || !M || iters < 0 ||
         (trim && !trim_args_ok(trim[0], trim[1], trim[2])))
         return set_error(ctx, PCP_ERR_ARG, "%s: bad arguments", who);
@@ -515,7 +515,10 @@ static int get_rot_plane(pcp_ctx* ctx, const char* who, const void* src, int64_t
     bufs.free(nrm);
     double T[24] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0};
     PCP_HIP(ctx, hipMemcpyAsync(pose, T, npose * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (trim)
+    if (trim && by_plane)
+        PCP_TRY(pcp_icp_run_plane_rtrimmed_dev(ctx, h.icp, h.planes, ft, 3 * sizeof(float), nt, pose, rmax, trim[0],
+                                               trim[1], trim[2], iters, pose + 16, (uint64_t*)(pose + 20)));
+    else if (trim)
         PCP_TRY(pcp_icp_run_plane_trimmed_dev(ctx, h.icp, h.planes, ft, 3 * sizeof(float), nt, pose, rmax, trim[0],
                                               trim[1], trim[2], iters, pose + 16, (uint64_t*)(pose + 20)));
     else
@@ -542,8 +545,8 @@ static int get_rot_plane(pcp_ctx* ctx, const char* who, const void* src, int64_t
 int pcp_get_rot_icp_plane(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, const void* tmp, int64_t nt,
                           int tmp_dense, double M[16], float rmax, int iters, int normals_k, double cell_size,
                           float* err) {
-    return get_rot_plane(ctx, "pcp_get_rot_icp_plane", src, ns, src_dense, tmp, nt, tmp_dense, M, rmax, nullptr, iters,
-                         normals_k, cell_size, err, nullptr);
+    return get_rot_plane(ctx, "pcp_get_rot_icp_plane", src, ns, src_dense, tmp, nt, tmp_dense, M, rmax, nullptr, false,
+                         iters, normals_k, cell_size, err, nullptr);
 }
 
 int pcp_get_rot_icp_plane_trimmed(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, const void* tmp, int64_t nt,
@@ -551,7 +554,15 @@ int pcp_get_rot_icp_plane_trimmed(pcp_ctx* ctx, const void* src, int64_t ns, int
                                   int iters, int normals_k, double cell_size, float* err, int64_t* kept_out) {
     const float trim[3] = {frac, mult, d_floor};
     return get_rot_plane(ctx, "pcp_get_rot_icp_plane_trimmed", src, ns, src_dense, tmp, nt, tmp_dense, M, rmax, trim,
-                         iters, normals_k, cell_size, err, kept_out);
+                         false, iters, normals_k, cell_size, err, kept_out);
+}
+
+int pcp_get_rot_icp_plane_rtrimmed(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, const void* tmp, int64_t nt,
+                                   int tmp_dense, double M[16], float rmax, float frac, float mult, float d_floor,
+                                   int iters, int normals_k, double cell_size, float* err, int64_t* kept_out) {
+    const float trim[3] = {frac, mult, d_floor};
+    return get_rot_plane(ctx, "pcp_get_rot_icp_plane_rtrimmed", src, ns, src_dense, tmp, nt, tmp_dense, M, rmax, trim,
+                         true, iters, normals_k, cell_size, err, kept_out);
 }
 
 }  // extern "C"

@@ -163,6 +163,10 @@ size_t trim_work_bytes();
 bool trim_args_ok(float frac, float mult, float d_floor);
 int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
                     uint64_t* out, uint64_t* trim, uint32_t* work);
+// its selection alone: trim = {m, 0, sel, bits of cut}; a filter of the caller's adds the kept keys
+// to trim[1] (n == 0: the complete stats)
+int trim_select_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
+                      uint64_t* trim, uint32_t* work);
 
 // Exclusive scan of `n` uint32 values in place (values' total must fit uint32).
 // Returns the total through *total_dev (device, optional) and *total_host (optional, syncs).

@@ -3,7 +3,8 @@
 // (pcp_icp_keys_dev) and does the minimisation: a packed {point, normal} table of the target,
 // the 30 accumulators of sum (n . (T q - p))^2 linearised at the pose, the scaled 6x6 LDL^T
 // solve, and the device loop around the three (with the trim of icp_trim.hip between the keys and
-// the accumulation in its trimmed form, pcp.h I3).
+// the accumulation in its trimmed form, pcp.h I3, or that trim's select over the pairs' squared
+// plane residuals between the residual and filter passes here, I3b).
 //
 // The accumulation's cost is its gather: one 32-byte record per pair at a data-dependent index,
 // both halves in one 64-byte line (two arrays would cost two lines).  Everything else streams.
@@ -123,6 +124,72 @@ __global__ void __launch_bounds__(kPB) k_acc_plane(const double* T, const float*
         double v = 0.0;
         for (int w = 0; w < kPB / 64; w++) v += sm[w][threadIdx.x];
         partials[(int64_t)blockIdx.x * kPAcc + threadIdx.x] = v;
+    }
+}
+
+// Residual pass of the trim by plane residual (pcp.h, I3b): per pair the key the select of
+// icp_trim.hip ranks, (bits of (float)(r * r) << 32) | target index for a usable pair and the "no
+// pair" key otherwise.  The pose, the fmaf chain, the record test and r are k_acc_plane's, in its
+// operation order, so r is the value the accumulation squares; r -> -r under a negated normal, and
+// r * r is then the same product.
+__global__ void __launch_bounds__(kPB) k_res_keys(const double* T, const float* q, size_t qs, int64_t n,
+                                                  const uint64_t* keys, const float4* rec, uint64_t nrec,
+                                                  uint64_t* rkeys) {
+    float R[9], t[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) R[3 * r + c] = (float)T[4 * r + c];
+        t[r] = (float)T[4 * r + 3];
+    }
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = keys[i];
+        const uint64_t j = key & 0xffffffffull;
+        uint64_t out = kNoKey;
+        if (key != kNoKey && j < nrec) {
+            const float4 pn = rec[2 * j + 1];
+            if (plane_valid(pn.x, pn.y, pn.z)) {
+                const float4 pp = rec[2 * j];
+                const float* qp = q + (size_t)i * qs;
+                const float x = __fmaf_rn(R[2], qp[2], __fmaf_rn(R[1], qp[1], __fmaf_rn(R[0], qp[0], t[0])));
+                const float y = __fmaf_rn(R[5], qp[2], __fmaf_rn(R[4], qp[1], __fmaf_rn(R[3], qp[0], t[1])));
+                const float z = __fmaf_rn(R[8], qp[2], __fmaf_rn(R[7], qp[1], __fmaf_rn(R[6], qp[0], t[2])));
+                const double qx = x, qy = y, qz = z, nx = pn.x, ny = pn.y, nz = pn.z;
+                const double r = (nx * (qx - (double)pp.x) + ny * (qy - (double)pp.y)) + nz * (qz - (double)pp.z);
+                const float rho = (float)(r * r);
+                if (rho == rho) out = ((uint64_t)__float_as_uint(rho) << 32) | j;
+            }
+        }
+        rkeys[i] = out;
+    }
+}
+
+// Filter and merge in one pass: k_trim_filter's keep rule read from the residual keys (usable and
+// as_float(high word) <= the select's cut), its count added to trim[1], and the result applied to
+// the caller's keys: a kept key is the caller's, all 64 bits.  In place only the rejected keys
+// are stored.
+__global__ void __launch_bounds__(kPB) k_res_filter(const uint64_t* keys, const uint64_t* rkeys, int64_t n,
+                                                    uint64_t* out, int inplace, uint64_t* trim) {
+    const float cut = __uint_as_float((uint32_t)trim[3]);
+    uint32_t cnt = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t rk = rkeys[i];
+        const bool keep = rk != kNoKey && __uint_as_float((uint32_t)(rk >> 32)) <= cut;
+        cnt += keep ? 1u : 0u;
+        if (inplace) {
+            if (!keep) out[i] = kNoKey;
+        } else {
+            out[i] = keep ? keys[i] : kNoKey;
+        }
+    }
+    __shared__ uint32_t sm[kPB / 64];
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < kPB / 64; w++) t += sm[w];
+        if (t) atomicAdd((unsigned long long*)&trim[1], (unsigned long long)t);
     }
 }
 
@@ -281,11 +348,29 @@ void launch_acc(pcp_ctx* ctx, const double* T_dev, const float* q, size_t q_stri
                        (const float4*)pl->rec, (uint64_t)pl->n, part);
 }
 
-// iters x (keys, [trim in place: trim = {frac, mult, d_floor}, stats of the last one to trim_dev,]
-// accumulate, sum + solve) on ctx's stream with no host round trip
+// pcp_icp_trim_keys_plane for callers that have checked the arguments and own the temporaries:
+// rkeys (n residual keys) and the select's work memory
+int trim_plane_async(pcp_ctx* ctx, const double* T_dev, const float* q, size_t q_stride, int64_t n,
+                     const uint64_t* keys, const pcp_icp_planes* pl, float frac, float mult, float d_floor,
+                     uint64_t* out, uint64_t* trim, uint64_t* rkeys, uint32_t* work) {
+    const int nb = acc_blocks(n);
+    if (n > 0)
+        hipLaunchKernelGGL(k_res_keys, dim3(nb), dim3(kPB), 0, ctx->stream, T_dev, q, q_stride / sizeof(float), n,
+                           keys, (const float4*)pl->rec, (uint64_t)pl->n, rkeys);
+    PCP_TRY(trim_select_async(ctx, rkeys, n, frac, mult, d_floor, trim, work));
+    if (n > 0)
+        hipLaunchKernelGGL(k_res_filter, dim3(nb), dim3(kPB), 0, ctx->stream, keys, (const uint64_t*)rkeys, n, out,
+                           out == keys ? 1 : 0, trim);
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
+// iters x (keys, [trim in place: trim = {frac, mult, d_floor}, by the point distance (I3) or, with
+// by_plane, by the plane residual (I3b); stats of the last one to trim_dev,] accumulate, sum +
+// solve) on ctx's stream with no host round trip
 int run_plane_loop(pcp_ctx* ctx, const char* who, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
-                   size_t q_stride, int64_t nq, double* T_dev, float rmax, const float* trim, int iters,
-                   double* stats_dev, uint64_t* trim_dev) {
+                   size_t q_stride, int64_t nq, double* T_dev, float rmax, const float* trim, bool by_plane,
+                   int iters, double* stats_dev, uint64_t* trim_dev) {
     if (!ctx || !icp || !planes || nq < 0 || (nq > 0 && !q_dev) || !T_dev || !stats_dev || iters < 0 ||
         !(rmax >= 0.f))
         return PCP_ERR_ARG;
@@ -304,10 +389,16 @@ int run_plane_loop(pcp_ctx* ctx, const char* who, pcp_icp* icp, const pcp_icp_pl
     uint32_t* work = nullptr;
     PCP_TRY(tmp.get(&keys, (size_t)nq));
     PCP_TRY(tmp.get(&part, (size_t)nb * kPAcc));
+    uint64_t* rkeys = nullptr;
     if (trim) PCP_TRY(tmp.get(&work, trim_work_bytes() / sizeof(uint32_t)));
+    if (trim && by_plane) PCP_TRY(tmp.get(&rkeys, (size_t)nq));
     for (int it = 0; it < iters; it++) {
         if (nq > 0) PCP_TRY(pcp_icp_keys_dev(ctx, icp, T_dev, rmax, 0, keys));
-        if (trim) PCP_TRY(trim_keys_async(ctx, keys, nq, trim[0], trim[1], trim[2], keys, trim_dev, work));
+        if (trim && by_plane)
+            PCP_TRY(trim_plane_async(ctx, T_dev, q_dev, q_stride, nq, keys, planes, trim[0], trim[1], trim[2], keys,
+                                     trim_dev, rkeys, work));
+        else if (trim)
+            PCP_TRY(trim_keys_async(ctx, keys, nq, trim[0], trim[1], trim[2], keys, trim_dev, work));
         launch_acc(ctx, T_dev, q_dev, q_stride, nq, keys, planes, nb, part);
         hipLaunchKernelGGL(k_plane_sum_solve, dim3(1), dim3(kPB), 0, ctx->stream, (const double*)part, nb, T_dev,
                            stats_dev);
@@ -396,8 +487,8 @@ int pcp_icp_solve_plane_dev(pcp_ctx* ctx, const double* acc_dev, double* T_dev, 
 
 int pcp_icp_run_plane_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
                           size_t q_stride, int64_t nq, double* T_dev, float rmax, int iters, double* stats_dev) {
-    return run_plane_loop(ctx, "pcp_icp_run_plane_dev", icp, planes, q_dev, q_stride, nq, T_dev, rmax, nullptr, iters,
-                          stats_dev, nullptr);
+    return run_plane_loop(ctx, "pcp_icp_run_plane_dev", icp, planes, q_dev, q_stride, nq, T_dev, rmax, nullptr, false,
+                          iters, stats_dev, nullptr);
 }
 
 int pcp_icp_run_plane_trimmed_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
@@ -406,7 +497,34 @@ int pcp_icp_run_plane_trimmed_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_plan
     if (!trim_dev || !trim_args_ok(frac, mult, d_floor)) return PCP_ERR_ARG;
     const float trim[3] = {frac, mult, d_floor};
     return run_plane_loop(ctx, "pcp_icp_run_plane_trimmed_dev", icp, planes, q_dev, q_stride, nq, T_dev, rmax, trim,
-                          iters, stats_dev, trim_dev);
+                          false, iters, stats_dev, trim_dev);
+}
+
+// as pcp_icp_trim_keys, the argument checks before the stride's read nothing through ctx
+int pcp_icp_trim_keys_plane(pcp_ctx* ctx, const double* T_dev, const float* q_dev, size_t q_stride, int64_t n,
+                            const uint64_t* keys_dev, const pcp_icp_planes* planes, float frac, float mult,
+                            float d_floor, uint64_t* keys_out_dev, uint64_t* trim_dev) {
+    if (!ctx || !trim_dev || !T_dev || !planes || n < 0 || n >= (int64_t)1 << 31 ||
+        (n > 0 && (!q_dev || !keys_dev || !keys_out_dev)) || !trim_args_ok(frac, mult, d_floor))
+        return PCP_ERR_ARG;
+    PCP_TRY(check_stride(ctx, &q_stride));
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    Tmp tmp(ctx);
+    uint64_t* rkeys = nullptr;
+    uint32_t* work = nullptr;
+    PCP_TRY(tmp.get(&rkeys, (size_t)n));
+    PCP_TRY(tmp.get(&work, trim_work_bytes() / sizeof(uint32_t)));
+    return trim_plane_async(ctx, T_dev, q_dev, q_stride, n, keys_dev, planes, frac, mult, d_floor, keys_out_dev,
+                            trim_dev, rkeys, work);
+}
+
+int pcp_icp_run_plane_rtrimmed_dev(pcp_ctx* ctx, pcp_icp* icp, const pcp_icp_planes* planes, const float* q_dev,
+                                   size_t q_stride, int64_t nq, double* T_dev, float rmax, float frac, float mult,
+                                   float d_floor, int iters, double* stats_dev, uint64_t* trim_dev) {
+    if (!trim_dev || !trim_args_ok(frac, mult, d_floor)) return PCP_ERR_ARG;
+    const float trim[3] = {frac, mult, d_floor};
+    return run_plane_loop(ctx, "pcp_icp_run_plane_rtrimmed_dev", icp, planes, q_dev, q_stride, nq, T_dev, rmax, trim,
+                          true, iters, stats_dev, trim_dev);
 }
 
 }  // extern "C"

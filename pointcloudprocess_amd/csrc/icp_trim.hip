@@ -216,8 +216,8 @@ bool trim_args_ok(float frac, float mult, float d_floor) {
            std::isfinite(d_floor);
 }
 
-int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
-                    uint64_t* out, uint64_t* trim, uint32_t* work) {
+int trim_select_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
+                      uint64_t* trim, uint32_t* work) {
     if (n == 0) {
         hipLaunchKernelGGL(k_trim_empty, dim3(1), dim3(1), 0, ctx->stream, d_floor, trim);
         PCP_LAUNCH_CHECK(ctx);
@@ -227,6 +227,14 @@ int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, f
     launch_pass<0>(ctx, keys, n, frac, mult, d_floor, trim, work);
     launch_pass<1>(ctx, keys, n, frac, mult, d_floor, trim, work);
     launch_pass<2>(ctx, keys, n, frac, mult, d_floor, trim, work);
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
+int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
+                    uint64_t* out, uint64_t* trim, uint32_t* work) {
+    PCP_TRY(trim_select_async(ctx, keys, n, frac, mult, d_floor, trim, work));
+    if (n == 0) return PCP_OK;
     hipLaunchKernelGGL(k_trim_filter, dim3(grid_for(n, kTB, kTFilterBlocks)), dim3(kTB), 0, ctx->stream, keys, n, out,
                        out == keys ? 1 : 0, trim);
     PCP_LAUNCH_CHECK(ctx);

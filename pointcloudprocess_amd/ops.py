@@ -444,6 +444,19 @@ class ICP:
                                                         _ptr(stats), _ptr(trim)))
         return trim
 
+    def run_plane_rtrimmed_dev(self, planes, q, T_dev, stats, rmax, frac, mult=1.0, d_floor=0.0, iters=4, trim=None):
+        """run_plane_trimmed_dev with icp_trim_keys_plane in place of icp_trim_keys: every iteration
+        trims by the pairs' plane residual at its pose (pcp.h I3b).  Returns trim as there."""
+        ctx = self.ctx
+        n = q.shape[0]
+        trim = torch.zeros(4, dtype=torch.int64, device=ctx.device) if trim is None else trim
+        assert trim.dtype == torch.int64 and trim.numel() >= 4
+        ctx.check(ctx.lib.pcp_icp_run_plane_rtrimmed_dev(ctx.h, self.h, planes.h, _ptr(q) if n else None,
+                                                         q.stride(0) * q.element_size(), n, _ptr(T_dev), float(rmax),
+                                                         float(frac), float(mult), float(d_floor), int(iters),
+                                                         _ptr(stats), _ptr(trim)))
+        return trim
+
     def kernel_ms(self):
         """(ms, launches) of the device-loop correspondence kernels since the last call."""
         ms, n = C.c_double(), C.c_int()
@@ -605,6 +618,23 @@ def icp_trim_keys(ctx, keys, frac, mult=1.0, d_floor=0.0, out=None):
     return out, trim
 
 
+def icp_trim_keys_plane(ctx, T_dev, q, keys, planes, frac, mult=1.0, d_floor=0.0, out=None):
+    """Trim correspondence keys by the plane residual (pcp.h I3b): keep the usable pairs of the
+    queries q (n x 3 fp32, original order) whose squared residual (n . (T q - p))^2 under the device
+    pose T_dev is <= max(mult^2 * the frac-quantile of those residuals, d_floor^2); the other keys
+    become INT64_MAX, the kept ones stay as they are.  out and the return values as icp_trim_keys."""
+    n = q.shape[0]
+    out = torch.empty_like(keys) if out is None else out
+    assert keys.dtype == torch.int64 and out.dtype == torch.int64 and keys.numel() >= n and out.numel() >= n
+    assert keys.is_contiguous() and out.is_contiguous()
+    trim = torch.zeros(4, dtype=torch.int64, device=ctx.device)
+    ctx.check(ctx.lib.pcp_icp_trim_keys_plane(ctx.h, _ptr(T_dev), _ptr(q) if n else None,
+                                              q.stride(0) * q.element_size(), n, _ptr(keys) if n else None, planes.h,
+                                              float(frac), float(mult), float(d_floor), _ptr(out) if n else None,
+                                              _ptr(trim)))
+    return out, trim
+
+
 def icp_solve_plane(acc):
     """Host 6x6 solve of 30 plane accumulators: (rc, dT); rc = -6 (PCP_ERR_ICP) and the identity
     for a numerically singular system."""
@@ -647,4 +677,18 @@ def get_rot_icp_plane_trimmed(ctx, src, temp, rmax, frac, mult=1.0, d_floor=0.0,
                                                     temp.shape[0], int(temp_dense), M, float(rmax), float(frac),
                                                     float(mult), float(d_floor), int(iters), int(normals_k),
                                                     float(cell_size), C.byref(err), C.byref(kept)))
+    return float(err.value), np.array(M[:]).reshape(4, 4), int(kept.value)
+
+
+def get_rot_icp_plane_rtrimmed(ctx, src, temp, rmax, frac, mult=1.0, d_floor=0.0, iters=4, normals_k=16,
+                               cell_size=0.0, src_dense=True, temp_dense=True):
+    """get_rot_icp_plane_trimmed through the loop that trims by the plane residual (pcp.h I3b):
+    (err, M, kept) as there."""
+    M = (C.c_double * 16)()
+    err = C.c_float()
+    kept = C.c_int64()
+    ctx.check(ctx.lib.pcp_get_rot_icp_plane_rtrimmed(ctx.h, _ptr(src), src.shape[0], int(src_dense), _ptr(temp),
+                                                     temp.shape[0], int(temp_dense), M, float(rmax), float(frac),
+                                                     float(mult), float(d_floor), int(iters), int(normals_k),
+                                                     float(cell_size), C.byref(err), C.byref(kept)))
     return float(err.value), np.array(M[:]).reshape(4, 4), int(kept.value)
