@@ -602,6 +602,87 @@ int pcp_get_rot_icp_plane_rtrimmed(pcp_ctx* ctx, const void* src_aos48_dev, int6
                                    float d_floor, int iters, int normals_k, double cell_size, float* err,
                                    int64_t* kept_out);
 
+/* ----------------------------------------------------------------------- I5: batched registration
+ * Many frame-sized query sets against ONE target in one launch chain (the reference re-registers
+ * every frame of a span on its own: do_mul_frame_icp with is_do_sep_icp, process_loop_icp,
+ * find_reliable).  A pcp_icp handle costs a sort, its allocations and about ten dependent launches
+ * per iteration whatever its size; here B segments with B device poses share one fp32 target
+ * index and one plane table, and an iteration is three launches whatever B is.  The single-pair
+ * handle, with its neighbour cache, stays the path for large query sets.  The point-to-plane
+ * contract is I2's, per segment.
+ *
+ * Segments.  Segment s is the queries [seg_offsets[s], seg_offsets[s + 1]) of q_dev (fp32 xyz,
+ *   stride 0 = 12).  seg_offsets_host has nseg + 1 entries, starts at 0, ends at nq and never
+ *   decreases; empty segments are legal, and so are nseg == 0 (then nq == 0) and nq == 0.
+ *   pcp_icp_batch_create copies the queries (q_dev may be released after it returns) and waits for
+ *   the stream.  PCP_ERR_ARG for: a null context, target, seg_offsets_host or out; a null q_dev with
+ *   nq > 0; nq < 0 or nq >= 2^31; nseg < 0 or nseg > 65535; offsets that break the rule above; a
+ *   stride that is not a whole number of floats or is below 12; a target that is not an fp32 index.
+ *   The target's size limits are pcp_icp_check_sizes's, its grid's pcp_icp_create's.  The handle
+ *   holds a reference on its context and borrows the target, as pcp_icp does; it owns three
+ *   allocator blocks, returned by pcp_icp_batch_destroy, so pcp_ctx_alloc_stats balances.  Per-call
+ *   temporaries of every entry come from the per-call guard, error paths included.
+ *
+ * Poses.  T_dev is nseg x 16 doubles: segment s has the row-major 4x4 at T_dev + 16 s.  stats_dev
+ *   is nseg x 4 doubles, zeroed by the caller: row s is pcp_icp_solve_plane_dev's stats of segment s.
+ *
+ * pcp_icp_batch_keys_dev writes keys_dev[i] for every query i < nq, in the ORIGINAL order.  The
+ *   keys of segment s are, bit for bit, what pcp_icp_keys_dev(ctx, h_s, T_dev + 16 s, rmax, 0, ..)
+ *   writes for a pcp_icp h_s created over that segment's queries alone on the same target:
+ *     R, t = the pose's 3x4 cast to fp32;
+ *     q'x = fmaf(R02, qz, fmaf(R01, qy, fmaf(R00, qx, t0))), rows 1 and 2 alike (fp32, round to
+ *       nearest);
+ *     d2(j) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) with d = q' - p_j in fp32, over EVERY finite
+ *       target point p_j (j its caller index);
+ *     the winner is the lexicographic minimum of (d2, j): the nearest point, the lower caller
+ *       index among equal d2 (duplicate points included);
+ *     r2 = rmax * rmax in fp32; the pair is accepted iff d2 <= r2 (equality accepts);
+ *     key = (bits of the winner's d2) << 32 | j when accepted; INT64_MAX when the query has a
+ *       non-finite coordinate, its image q' has one, or no target lies within rmax.
+ *   The search is exact for every rmax >= 0 and every pose: rmax many cells wide, images outside
+ *   the grid's box, dense and brick (sparse) cell tables.  A segment whose pose is a large rotation
+ *   loses the locality of the create-time sort; that costs time, never exactness.  PCP_ERR_ARG for
+ *   null pointers and !(rmax >= 0).
+ *
+ * pcp_icp_batch_accumulate_plane: row s of acc_dev (nseg x 30) is the 30 sums of I2
+ *   (pcp_icp_accumulate_plane) over segment s's queries at the pose T_dev + 16 s, paired through
+ *   keys_dev (nq keys, original order): the same per-pair arithmetic and the same skips (INT64_MAX,
+ *   an index at or past the table's size, an invalid record).  An empty segment writes 30 zeros.
+ *   The sum's order is fixed by the handle alone (per 64-query chunk of the segment's sorted
+ *   queries a butterfly over the lanes, then the chunks in a fixed order): bit for bit the same on
+ *   every run, with no float atomics, and independent of the other segments.  It is a plain sum,
+ *   but its order is not pcp_icp_accumulate_plane's: the two agree to rounding, not bit for bit.
+ *
+ * pcp_icp_batch_solve_plane_dev: device thread s runs pcp_icp_solve_plane_dev's solve on row s of
+ *   acc_dev, T_dev + 16 s and stats_dev + 4 s.  A failed solve latches stats[4 s] = -1 and freezes
+ *   that segment's pose only (its stats[4 s + 1 .. 3] stay as they were); the others carry on.  An
+ *   empty segment, or one with fewer than 6 pairs, fails.
+ *
+ * pcp_icp_batch_run_plane_dev = iters x (keys, accumulate, solve) over all segments on the context's
+ *   stream, with no host round trip and no allocation inside the loop: three launches per iteration
+ *   whatever nseg is, and poses bit-identical to calling the three entries in turn.  The plane
+ *   table's size must be the target index's caller size (PCP_ERR_ARG otherwise).
+ *
+ * Not here: the point-to-point minimisation, and the trimmed loops of I3 / I3b.  pcp_icp_trim_keys
+ * over a batch's keys takes ONE quantile across all segments, not one per segment; a segmented
+ * select is future work. */
+typedef struct pcp_icp_batch pcp_icp_batch;
+int pcp_icp_batch_create(pcp_ctx* ctx, const pcp_index* target, const float* q_dev, size_t q_stride_bytes,
+                         int64_t nq, const int64_t* seg_offsets_host /* nseg + 1 */, int nseg,
+                         pcp_icp_batch** out);
+int pcp_icp_batch_destroy(pcp_icp_batch* batch);
+int64_t pcp_icp_batch_queries(const pcp_icp_batch* batch);  /* nq as passed */
+int pcp_icp_batch_segments(const pcp_icp_batch* batch);
+int pcp_icp_batch_keys_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const double* T_dev /* nseg x 16 */, float rmax,
+                           uint64_t* keys_dev /* nq, ORIGINAL order */);
+int pcp_icp_batch_accumulate_plane(pcp_ctx* ctx, pcp_icp_batch* batch, const double* T_dev,
+                                   const uint64_t* keys_dev, const pcp_icp_planes* planes,
+                                   double* acc_dev /* nseg x 30 */);
+int pcp_icp_batch_solve_plane_dev(pcp_ctx* ctx, const double* acc_dev, int nseg, double* T_dev,
+                                  double* stats_dev /* nseg x 4 */);
+int pcp_icp_batch_run_plane_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const pcp_icp_planes* planes, double* T_dev,
+                                float rmax, int iters, double* stats_dev /* nseg x 4, zeroed by the caller */);
+
 /* ----------------------------------------------------------------------- I4: pose lines
  * Host-only (no device work): n frames' poses as row-major 4x4 doubles, rots[16 * i].
  *

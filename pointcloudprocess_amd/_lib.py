@@ -130,6 +130,14 @@ SIGNATURES = [
                                               _vp, _vp]),
     ("pcp_get_rot_icp_plane_rtrimmed", _i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _P(_f64), _f32, _f32, _f32,
                                               _f32, _i32, _i32, _f64, _P(_f32), _P(_i64)]),
+    ("pcp_icp_batch_create", _i32, [_vp, _vp, _vp, _sz, _i64, _P(_i64), _i32, _P(_vp)]),
+    ("pcp_icp_batch_destroy", _i32, [_vp]),
+    ("pcp_icp_batch_queries", _i64, [_vp]),
+    ("pcp_icp_batch_segments", _i32, [_vp]),
+    ("pcp_icp_batch_keys_dev", _i32, [_vp, _vp, _vp, _f32, _vp]),
+    ("pcp_icp_batch_accumulate_plane", _i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("pcp_icp_batch_solve_plane_dev", _i32, [_vp, _vp, _i32, _vp, _vp]),
+    ("pcp_icp_batch_run_plane_dev", _i32, [_vp, _vp, _vp, _vp, _f32, _i32, _vp]),
 ]
 
 _lib = None

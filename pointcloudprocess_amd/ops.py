@@ -603,6 +603,84 @@ def icp_accumulate_plane(ctx, T_dev, q, keys, planes, acc=None):
     return acc
 
 
+class ICPBatch:
+    """pcp_icp_batch (pcp.h I5): B query segments registered against one fp32 target index, one
+    device pose per segment, three launches per point-to-plane iteration whatever B is.  q: (n, >= 3)
+    fp32 device tensor; seg_offsets: B + 1 non-decreasing integers from 0 to n (segment s is
+    q[seg_offsets[s]:seg_offsets[s + 1]]).  Keys are in q's order."""
+
+    def __init__(self, target_index, q, seg_offsets):
+        self.index = target_index
+        self.ctx = ctx = target_index.ctx
+        off = [int(v) for v in seg_offsets]
+        if not off:
+            raise ValueError("seg_offsets needs at least one entry")
+        self.nseg = len(off) - 1
+        self.nq = n = q.shape[0]
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pcp_icp_batch_create(ctx.h, target_index.h, _ptr(q) if n else None,
+                                               q.stride(0) * q.element_size(), n, (C.c_int64 * len(off))(*off),
+                                               self.nseg, C.byref(h)))
+        self.h = h
+
+    def new_poses(self, T0=None):
+        """(T_dev, stats): device poses (B, 16) fp64 row-major -- the identity, one 4x4 for all, or
+        B of them -- and zeroed stats (B, 4)."""
+        B = self.nseg
+        T = np.eye(4) if T0 is None else np.asarray(T0, dtype=np.float64)
+        T = np.broadcast_to(T.reshape(-1, 16), (B, 16)) if T.size == 16 else T.reshape(B, 16)
+        return (torch.as_tensor(np.array(T), dtype=torch.float64).to(self.ctx.device).contiguous(),
+                torch.zeros((B, 4), dtype=torch.float64, device=self.ctx.device))
+
+    def _check_poses(self, T_dev, stats=None):
+        assert T_dev.dtype == torch.float64 and T_dev.numel() >= 16 * self.nseg and T_dev.is_contiguous()
+        if stats is not None:
+            assert stats.dtype == torch.float64 and stats.numel() >= 4 * self.nseg and stats.is_contiguous()
+
+    def keys_dev(self, T_dev, rmax, out=None):
+        """Per query (q's order) the int64 key of its exact nearest target within rmax under its
+        segment's pose, INT64_MAX for none: per segment, ICP.keys_dev's keys bit for bit."""
+        ctx = self.ctx
+        keys = torch.empty(self.nq, dtype=torch.int64, device=ctx.device) if out is None else out
+        assert keys.dtype == torch.int64 and keys.numel() >= self.nq and keys.is_contiguous()
+        self._check_poses(T_dev)
+        ctx.check(ctx.lib.pcp_icp_batch_keys_dev(ctx.h, self.h, _ptr(T_dev), float(rmax), _ptr(keys)))
+        return keys
+
+    def accumulate_plane(self, T_dev, keys, planes, acc=None):
+        """(B, 30): per segment the point-to-plane accumulators of icp_accumulate_plane."""
+        ctx = self.ctx
+        acc = torch.zeros((self.nseg, 30), dtype=torch.float64, device=ctx.device) if acc is None else acc
+        assert acc.dtype == torch.float64 and acc.numel() >= 30 * self.nseg and acc.is_contiguous()
+        assert keys.dtype == torch.int64 and keys.numel() >= self.nq and keys.is_contiguous()
+        self._check_poses(T_dev)
+        ctx.check(ctx.lib.pcp_icp_batch_accumulate_plane(ctx.h, self.h, _ptr(T_dev), _ptr(keys), planes.h, _ptr(acc)))
+        return acc
+
+    def solve_plane_dev(self, acc, T_dev, stats):
+        """Per segment ICP.solve_plane_dev: T_dev[s] <- dT_s * T_dev[s]; a failed solve latches
+        stats[s, 0] = -1 and freezes that segment's pose only."""
+        ctx = self.ctx
+        assert acc.dtype == torch.float64 and acc.numel() >= 30 * self.nseg and acc.is_contiguous()
+        self._check_poses(T_dev, stats)
+        ctx.check(ctx.lib.pcp_icp_batch_solve_plane_dev(ctx.h, _ptr(acc), self.nseg, _ptr(T_dev), _ptr(stats)))
+
+    def run_plane_dev(self, planes, T_dev, stats, rmax, iters):
+        """iters x (keys_dev, accumulate_plane, solve_plane_dev) with no host round trip."""
+        ctx = self.ctx
+        self._check_poses(T_dev, stats)
+        ctx.check(ctx.lib.pcp_icp_batch_run_plane_dev(ctx.h, self.h, planes.h, _ptr(T_dev), float(rmax), int(iters),
+                                                      _ptr(stats)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pcp_icp_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 def icp_trim_keys(ctx, keys, frac, mult=1.0, d_floor=0.0, out=None):
     """Trim correspondence keys (pcp.h I3): keep the valid keys whose fp32 d2 (the high word) is <=
     max(mult^2 * the frac-quantile of the valid d2, d_floor^2); the others become INT64_MAX.
