@@ -142,6 +142,14 @@ inline unsigned grid_for(int64_t n, int block, int64_t cap = 1 << 20) {
     return (unsigned)g;
 }
 
+// a caller's byte stride between xyz triples: 0 means packed; whole floats, at least 3
+inline int check_stride(pcp_ctx* ctx, size_t* stride) {
+    if (*stride == 0) *stride = 3 * sizeof(float);
+    if (*stride % sizeof(float) || *stride < 3 * sizeof(float))
+        return set_error(ctx, PCP_ERR_ARG, "strides must be whole floats, at least 3");
+    return PCP_OK;
+}
+
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ bool finite3(double x, double y, double z) {
     return isfinite(x) && isfinite(y) && isfinite(z);
@@ -167,6 +175,10 @@ int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, f
 // to trim[1] (n == 0: the complete stats)
 int trim_select_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
                       uint64_t* trim, uint32_t* work);
+// the filter after it: out[i] = keys[i] where the key ranked for pair i passes trim's cut, else "no
+// pair"; the ranked key is rkeys[i], or keys[i] itself when rkeys is null.  out may be keys.
+int trim_filter_async(pcp_ctx* ctx, const uint64_t* keys, const uint64_t* rkeys, int64_t n, uint64_t* out,
+                      uint64_t* trim);
 
 // Exclusive scan of `n` uint32 values in place (values' total must fit uint32).
 // Returns the total through *total_dev (device, optional) and *total_host (optional, syncs).

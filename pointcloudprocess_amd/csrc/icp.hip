@@ -8,6 +8,11 @@
 // 24 double accumulators reduced per wavefront (shuffles) -> per workgroup (LDS) -> one
 // fixed-order pass over the workgroup partials.  The host solves the 3x3 Kabsch/Umeyama
 // problem (pcp_icp_solve) and composes the pose.
+//
+// Owned here: the handle, the search kernels and their caches, the look-ahead pose block, the 3x3
+// solve, and the loops of the target-sharded key kernels (k_make_keys, k_acc_keys, k_acc_owned).
+// The search arithmetic is icp_search.hpp's; the key's layout, the pose cast, the Kabsch terms of
+// a pair and the block reductions of the key kernels are icp_pair.hpp's.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -17,8 +22,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 #include "sortcfg.hpp"
 
-#include "grid.hpp"
-#include "icp_search.hpp"
+#include "icp_pair.hpp"
 #include "wave_acc.hpp"
 
 namespace pcp {
@@ -98,7 +102,6 @@ constexpr int kIcpBlock = 256;
 #ifndef PCP_RING_WAVES
 #define PCP_RING_WAVES 6
 #endif
-constexpr int kAcc = 24;
 
 struct IcpArgs {
     GridDesc g;
@@ -1371,9 +1374,8 @@ __global__ void k_fill_corr(int32_t* idx, float* d2, int64_t n) {
 
 // ---- target-sharded mode: per-query u64 key = (fp32 bits of d2) << 32 |
 // global target index, so a MIN over ranks is the lexicographic (d2, index) winner (non-
-// negative fp32 bit patterns order like the values).  No correspondence = INT64_MAX.
-constexpr uint64_t kNoKey = 0x7fffffffffffffffull;
-
+// negative fp32 bit patterns order like the values).  No correspondence = INT64_MAX.  The layout
+// and what is done with a pair are icp_pair.hpp's.
 __global__ void k_fill_keys(uint64_t* keys, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         keys[i] = kNoKey;
@@ -1387,17 +1389,16 @@ __global__ void k_make_keys(IcpArgs a, uint32_t offset, uint64_t* keys) {
         float x, y, z;
         xform(a, qq, x, y, z);
         const CacheBest w = cache_best(a.tp, cache_load(a, i), x, y, z);
-        keys[oq] = w.bd <= a.r2 ? (((uint64_t)__float_as_uint(w.bd) << 32) | (uint64_t)(uint32_t)((uint32_t)w.bj + offset))
-                                : kNoKey;
+        keys[oq] = w.bd <= a.r2 ? key_make(w.bd, (uint32_t)w.bj + offset) : kNoKey;
     }
 }
 
 // accumulators over the queries whose global winner lies in [lo, hi) (this rank's shard);
 // float products are exact in fp64, so only the summation order differs from the oracle
-__global__ void __launch_bounds__(256) k_acc_keys(const QXyz* q, const int32_t* qidx, int64_t n, const uint64_t* keys,
-                                                  uint64_t lo,
-                                                  uint64_t hi, const float* shard, size_t stride_f, IcpArgs a,
-                                                  double* partials) {
+__global__ void __launch_bounds__(kPairBlock) k_acc_keys(const QXyz* q, const int32_t* qidx, int64_t n,
+                                                         const uint64_t* keys, uint64_t lo, uint64_t hi,
+                                                         const float* shard, size_t stride_f, Pose32 P,
+                                                         double* partials) {
     double acc[kAcc - 1];
 #pragma unroll
     for (int k = 0; k < kAcc - 1; k++) acc[k] = 0.0;
@@ -1405,54 +1406,19 @@ __global__ void __launch_bounds__(256) k_acc_keys(const QXyz* q, const int32_t* 
         const float4 qq = make_float4(q[i].x, q[i].y, q[i].z, 0.f);
         const uint64_t key = keys[qidx[i]];
         if (key == kNoKey) continue;
-        const uint64_t g = key & 0xffffffffull;
+        const uint64_t g = key_index(key);
         if (g < lo || g >= hi) continue;
         const float* p = shard + (size_t)(g - lo) * stride_f;
         float x, y, z;
-        xform(a, qq, x, y, z);
+        xform(P, qq, x, y, z);
         const double qv[3] = {x, y, z}, pv[3] = {p[0], p[1], p[2]};
-        acc[0] += 1.0;
-#pragma unroll
-        for (int c = 0; c < 3; c++) { acc[1 + c] += qv[c]; acc[4 + c] += pv[c]; }
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) acc[7 + 3 * r + c] += qv[r] * pv[c];
-        acc[16] += qv[0] * qv[0]; acc[17] += qv[0] * qv[1]; acc[18] += qv[0] * qv[2];
-        acc[19] += qv[1] * qv[1]; acc[20] += qv[1] * qv[2]; acc[21] += qv[2] * qv[2];
-        acc[22] += (double)__uint_as_float((uint32_t)(key >> 32));
+        kabsch_terms(qv, pv, key, acc);
     }
-    __shared__ double sm[4][kAcc];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kAcc - 1; k++) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) sm[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kAcc) {
-        double v = 0.0;
-        if (threadIdx.x < kAcc - 1)
-            for (int w = 0; w < 4; w++) v += sm[w][threadIdx.x];
-        partials[(int64_t)blockIdx.x * kAcc + threadIdx.x] = v;
-    }
+    block_partials<kAcc - 1, kAcc>(acc, partials + (int64_t)blockIdx.x * kAcc);
 }
 
-__global__ void __launch_bounds__(256) k_sum_partials(const double* part, int nb, double* out) {
-    __shared__ double s[256];
-    for (int k = 0; k < kAcc; k++) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nb; b += 256) v += part[(int64_t)b * kAcc + k];
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[k] = s[0];
-        __syncthreads();
-    }
+__global__ void __launch_bounds__(kPairBlock) k_sum_partials(const double* part, int nb, double* out) {
+    sum_partials<kAcc>(part, nb, out);
 }
 
 // Target-sharded mode, device-resident form: after a ReduceScatter(MIN) of
@@ -1467,7 +1433,7 @@ __global__ void k_keys_owner(const uint64_t* keys, int64_t n, const int64_t* bou
         const uint64_t k = keys[i];
         uint8_t o = 255;
         if (k != kNoKey) {
-            const int64_t g = (int64_t)(k & 0xffffffffull);
+            const int64_t g = (int64_t)key_index(k);
             int lo = 0, hi = nshards;  // the last s with bounds[s] <= g
             while (hi - lo > 1) {
                 const int mid = (lo + hi) >> 1;
@@ -1482,58 +1448,28 @@ __global__ void k_keys_owner(const uint64_t* keys, int64_t n, const int64_t* bou
 
 // accumulators of the queries (original order, q) whose winner this rank owns: the winner is
 // the rank's local key's target (its global index less lo) -- for an owned query the local key
-// IS the global MIN.  The pose is the device 4x4 cast to fp32 as k_pose_set does; products of
-// fp32 values are exact in fp64, so only the summation order differs from the oracle.
-__global__ void __launch_bounds__(256) k_acc_owned(const double* T, const float* q, size_t qs, int64_t n,
-                                                   const uint64_t* keys, const uint8_t* owner, int rank, int64_t lo,
-                                                   int64_t hi, const float* shard, size_t ss, double* partials) {
-    float R[9], t[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) R[3 * r + c] = (float)T[4 * r + c];
-        t[r] = (float)T[4 * r + 3];
-    }
+// IS the global MIN.  The pose is pose32 of the device 4x4, the image xform's and the terms
+// kabsch_terms' (icp_pair.hpp), so only the summation order differs from the oracle.
+__global__ void __launch_bounds__(kPairBlock) k_acc_owned(const double* T, const float* q, size_t qs, int64_t n,
+                                                          const uint64_t* keys, const uint8_t* owner, int rank,
+                                                          int64_t lo, int64_t hi, const float* shard, size_t ss,
+                                                          double* partials) {
+    const Pose32 P = pose32(T);
     double acc[kAcc - 1];
 #pragma unroll
     for (int k = 0; k < kAcc - 1; k++) acc[k] = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         if (owner[i] != (uint8_t)rank) continue;
         const uint64_t key = keys[i];
-        const int64_t g = (int64_t)(key & 0xffffffffull);
+        const int64_t g = (int64_t)key_index(key);
         if (key == kNoKey || g < lo || g >= hi) continue;
-        const float* qp = q + (size_t)i * qs;
         const float* p = shard + (size_t)(g - lo) * ss;
-        const float x = __fmaf_rn(R[2], qp[2], __fmaf_rn(R[1], qp[1], __fmaf_rn(R[0], qp[0], t[0])));
-        const float y = __fmaf_rn(R[5], qp[2], __fmaf_rn(R[4], qp[1], __fmaf_rn(R[3], qp[0], t[1])));
-        const float z = __fmaf_rn(R[8], qp[2], __fmaf_rn(R[7], qp[1], __fmaf_rn(R[6], qp[0], t[2])));
+        float x, y, z;
+        xform(P, q + (size_t)i * qs, x, y, z);
         const double qv[3] = {x, y, z}, pv[3] = {p[0], p[1], p[2]};
-        acc[0] += 1.0;
-#pragma unroll
-        for (int c = 0; c < 3; c++) { acc[1 + c] += qv[c]; acc[4 + c] += pv[c]; }
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) acc[7 + 3 * r + c] += qv[r] * pv[c];
-        acc[16] += qv[0] * qv[0]; acc[17] += qv[0] * qv[1]; acc[18] += qv[0] * qv[2];
-        acc[19] += qv[1] * qv[1]; acc[20] += qv[1] * qv[2]; acc[21] += qv[2] * qv[2];
-        acc[22] += (double)__uint_as_float((uint32_t)(key >> 32));
+        kabsch_terms(qv, pv, key, acc);
     }
-    __shared__ double sm[4][kAcc];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kAcc - 1; k++) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) sm[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kAcc) {
-        double v = 0.0;
-        if (threadIdx.x < kAcc - 1)
-            for (int w = 0; w < 4; w++) v += sm[w][threadIdx.x];
-        partials[(int64_t)blockIdx.x * kAcc + threadIdx.x] = v;
-    }
+    block_partials<kAcc - 1, kAcc>(acc, partials + (int64_t)blockIdx.x * kAcc);
 }
 
 // co-partitioned slab guard (one thread): the owned queries' box [b0..b5] = {x0,x1,y0,y1,z0,z1}
@@ -1668,10 +1604,7 @@ __host__ __device__ double det3(const double M[9]) {
 
 // device poses for the kernels: pose[12..23] <- pose[0..11] (the previous launch's), then
 // pose[0..11] <- R, t of T_dev (row-major 4x4 doubles cast to fp32, as on the host) or of the
-// host-cast Rh/th when T_dev is null
-struct HostPose {
-    float R[9], t[3];
-};
+// host-cast hp (pose32) when T_dev is null
 // The look-ahead map.  ICP steps are almost collinear and shrink geometrically (ratio r per
 // launch), so a query's remaining path from q_t is about (q_t - q_{t-1}) r / (1 - r) along the
 // last step.  A search centred at c = T_c q, T_c = T_t + beta (T_t - T_{t-1}) with
@@ -1692,7 +1625,7 @@ struct LookAhead {
 #define PCP_LOOK_ALPHA 0.5f
 #endif
 constexpr float kLookAlpha = PCP_LOOK_ALPHA, kLookCap = 0.02f, kLookRmax = 0.9f;
-__global__ void k_pose_set(const double* T, HostPose hp, LookAhead la, float* pose, float* hist, uint32_t launch) {
+__global__ void k_pose_set(const double* T, Pose32 hp, LookAhead la, float* pose, float* hist, uint32_t launch) {
     *(uint32_t*)(pose + 24) = launch;
     for (int k = 0; k < 12; k++) pose[12 + k] = pose[k];
     for (int r = 0; r < 3; r++) {
@@ -1801,13 +1734,7 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     a.qidx = icp->qidx;
     a.nq = icp->nq;
     a.nchunks = (icp->nq + kIcpBlock - 1) / kIcpBlock;
-    HostPose hp{};
-    if (!T_dev) {
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) hp.R[3 * r + c] = (float)T[4 * r + c];
-            hp.t[r] = (float)T[4 * r + 3];
-        }
-    }
+    const Pose32 hp = T_dev ? Pose32{} : pose32(T);
     LookAhead la{};
     for (int k = 0; k < 3; k++) {
         la.lo[k] = (float)(a.g.o[k] - rmax);
@@ -2403,12 +2330,13 @@ int pcp_icp_accumulate_owned(pcp_ctx* ctx, const double* T_dev, const float* q_d
         return pcp::set_error(ctx, PCP_ERR_ARG, "strides must be whole floats");
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     const int nb = (int)std::min<int64_t>(std::max<int64_t>(1, (nq + 255) / 256), 2048);
+    pcp::Tmp tmp(ctx);
     double* part = nullptr;
-    PCP_TRY(pcp::dmalloc(ctx, &part, (size_t)nb * pcp::kAcc));
-    hipLaunchKernelGGL(pcp::k_acc_owned, dim3(nb), dim3(256), 0, ctx->stream, T_dev, q_dev, q_stride / sizeof(float),
-                       nq, keys_dev, owner_dev, rank, lo, hi, shard_xyz_dev, shard_stride / sizeof(float), part);
-    hipLaunchKernelGGL(pcp::k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, nb, acc_dev);
-    pcp::dfree(ctx, part);
+    PCP_TRY(tmp.get(&part, (size_t)nb * pcp::kAcc));
+    const dim3 block(pcp::kPairBlock);
+    hipLaunchKernelGGL(pcp::k_acc_owned, dim3(nb), block, 0, ctx->stream, T_dev, q_dev, q_stride / sizeof(float), nq,
+                       keys_dev, owner_dev, rank, lo, hi, shard_xyz_dev, shard_stride / sizeof(float), part);
+    hipLaunchKernelGGL(pcp::k_sum_partials, dim3(1), block, 0, ctx->stream, (const double*)part, nb, acc_dev);
     PCP_LAUNCH_CHECK(ctx);
     return PCP_OK;
 }
@@ -2430,17 +2358,12 @@ int pcp_icp_accumulate_keys(pcp_ctx* ctx, pcp_icp* icp, const double T[16], cons
     if (shard_stride_bytes == 0) shard_stride_bytes = 3 * sizeof(float);
     if (shard_stride_bytes % sizeof(float)) return pcp::set_error(ctx, PCP_ERR_ARG, "shard stride must be whole floats");
     PCP_HIP(ctx, hipSetDevice(ctx->device));
-    pcp::IcpArgs a{};
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) a.R[3 * r + c] = (float)T[4 * r + c];
-        a.t[r] = (float)T[4 * r + 3];
-    }
     const int nb = (int)std::min<int64_t>(std::max<int64_t>(1, (icp->nq + 255) / 256), icp->nb_fast + icp->nb_ring);
-    hipLaunchKernelGGL(pcp::k_acc_keys, dim3(nb), dim3(256), 0, ctx->stream, icp->q, icp->qidx, icp->nq, keys_dev,
-                       (uint64_t)lo, (uint64_t)hi, shard_xyz_dev, shard_stride_bytes / sizeof(float), a,
+    const dim3 block(pcp::kPairBlock);
+    hipLaunchKernelGGL(pcp::k_acc_keys, dim3(nb), block, 0, ctx->stream, icp->q, icp->qidx, icp->nq, keys_dev,
+                       (uint64_t)lo, (uint64_t)hi, shard_xyz_dev, shard_stride_bytes / sizeof(float), pcp::pose32(T),
                        icp->partials);
-    hipLaunchKernelGGL(pcp::k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, (const double*)icp->partials, nb,
-                       acc_dev);
+    hipLaunchKernelGGL(pcp::k_sum_partials, dim3(1), block, 0, ctx->stream, (const double*)icp->partials, nb, acc_dev);
     PCP_LAUNCH_CHECK(ctx);
     return PCP_OK;
 }

@@ -6,7 +6,9 @@
 // (segments are padded to whole chunks), so a wave reads its segment's pose through scalar loads
 // and reduces its accumulators without a segment test per lane.  There is no cache: a query runs
 // the exact row search of icp_search.hpp from the bound rmax^2, the arithmetic the single-pair
-// kernels use, so the keys are theirs bit for bit.
+// kernels use, so the keys are theirs bit for bit.  Owned here: the padded chunk layout, the three
+// kernels' loops and the per-segment sum; the pose cast, the key, the usable-pair test and the 30
+// terms are icp_pair.hpp's, the solve icp_plane_solve.hpp's.
 //
 //   k_batch_search      one query per lane: pose chain, box_search, key -> keys[original index]
 //   k_batch_acc         one chunk per wave: the 30 sums of the chunk's pairs -> partials[chunk]
@@ -16,9 +18,7 @@
 
 #include "sortcfg.hpp"
 
-#include "grid.hpp"
-#include "icp_plane_solve.hpp"
-#include "icp_search.hpp"
+#include "icp_pair.hpp"
 
 struct pcp_icp_batch {
     pcp_ctx* owner = nullptr;         // the creating context: owns the buffers (a lifetime reference)
@@ -37,22 +37,6 @@ namespace {
 constexpr int kBB = 256;          // 4 waves = 4 chunks per block
 constexpr int kBW = kBB / 64;
 constexpr int kSumGroups = 8;     // k_batch_sum_solve: chunk c of a segment is summed by group c % 8
-constexpr uint64_t kNoKey = 0x7fffffffffffffffull;
-
-struct BPose {
-    float R[9], t[3];
-};
-// row-major 4x4 doubles cast to fp32, as k_acc_plane and k_pose_set cast them.  T is wave-uniform.
-__device__ __forceinline__ BPose pose_of(const double* T) {
-    BPose p;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) p.R[3 * r + c] = (float)T[4 * r + c];
-        p.t[r] = (float)T[4 * r + 3];
-    }
-    return p;
-}
 
 // ---- create: sort key (segment, cell key at the identity) and the caller index as payload
 __global__ void __launch_bounds__(kBB) k_batch_sort_keys(GridDesc g, const float* q, size_t stride_f, int64_t n,
@@ -102,7 +86,7 @@ __global__ void __launch_bounds__(kBB) k_batch_search(GridDesc g, const float4* 
     const int64_t c = (int64_t)blockIdx.x * kBW + (threadIdx.x >> 6);
     if (c >= nch) return;
     const int s = __builtin_amdgcn_readfirstlane(chunk_seg[c]);
-    const BPose P = pose_of(T + 16 * (int64_t)s);
+    const Pose32 P = pose32(T + 16 * (int64_t)s);  // T is wave-uniform
     const float4 v = rec[c * 64 + lane];
     const int oi = __float_as_int(v.w);
     if (oi < 0) return;  // a pad slot
@@ -113,13 +97,13 @@ __global__ void __launch_bounds__(kBB) k_batch_search(GridDesc g, const float4* 
     if (isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(x) && isfinite(y) && isfinite(z)) {
         Best b{r2, 0x7fffffff, 0u, 0.f, 0.f, 0.f};
         box_search<1>(g, tp, x, y, z, mc, b);
-        if (b.bj != 0x7fffffff) key = ((uint64_t)__float_as_uint(b.bd) << 32) | (uint64_t)(uint32_t)b.bj;
+        if (b.bj != 0x7fffffff) key = key_make(b.bd, (uint32_t)b.bj);
     }
     keys[oi] = key;
 }
 
-// ---- accumulate: the per-pair arithmetic and skip rules of k_acc_plane (icp_plane.hip); the 30
-// terms of the chunk's 64 lanes are added by a butterfly, the same tree on every run
+// ---- accumulate: plane_pair's skip rule and plane_terms (icp_pair.hpp), as every plane consumer;
+// the 30 terms of the chunk's 64 lanes are added by a butterfly, the same tree on every run
 __global__ void __launch_bounds__(kBB) k_batch_acc(const float4* qrec, const int32_t* chunk_seg, int64_t nch,
                                                    const double* T, const uint64_t* keys, const float4* rec,
                                                    uint64_t nrec, double* partials) {
@@ -127,7 +111,7 @@ __global__ void __launch_bounds__(kBB) k_batch_acc(const float4* qrec, const int
     const int64_t c = (int64_t)blockIdx.x * kBW + (threadIdx.x >> 6);
     if (c >= nch) return;
     const int s = __builtin_amdgcn_readfirstlane(chunk_seg[c]);
-    const BPose P = pose_of(T + 16 * (int64_t)s);
+    const Pose32 P = pose32(T + 16 * (int64_t)s);  // T is wave-uniform
     const float4 v = qrec[c * 64 + lane];
     const int oi = __float_as_int(v.w);
     double term[kPAcc];
@@ -135,31 +119,11 @@ __global__ void __launch_bounds__(kBB) k_batch_acc(const float4* qrec, const int
     for (int k = 0; k < kPAcc; k++) term[k] = 0.0;
     if (oi >= 0) {
         const uint64_t key = keys[oi];
-        const uint64_t j = key & 0xffffffffull;
-        if (key != kNoKey && j < nrec) {
-            const float4 pn = rec[2 * j + 1];
-            if (plane_valid(pn.x, pn.y, pn.z)) {
-                const float4 pp = rec[2 * j];
-                float x, y, z;
-                xform(P, v, x, y, z);
-                const double qx = x, qy = y, qz = z, nx = pn.x, ny = pn.y, nz = pn.z;
-                double J[6];
-                J[0] = qy * nz - qz * ny;
-                J[1] = qz * nx - qx * nz;
-                J[2] = qx * ny - qy * nx;
-                J[3] = nx; J[4] = ny; J[5] = nz;
-                const double r = (nx * (qx - (double)pp.x) + ny * (qy - (double)pp.y)) + nz * (qz - (double)pp.z);
-                term[0] = 1.0;
-                int k = 1;
-#pragma unroll
-                for (int a = 0; a < 6; a++)
-#pragma unroll
-                    for (int b = a; b < 6; b++) term[k++] = J[a] * J[b];
-#pragma unroll
-                for (int a = 0; a < 6; a++) term[22 + a] = r * J[a];
-                term[28] = r * r;
-                term[29] = (double)__uint_as_float((uint32_t)(key >> 32));
-            }
+        PlanePair pr;
+        if (plane_pair(key, rec, nrec, pr)) {
+            float x, y, z;
+            xform(P, v, x, y, z);
+            plane_terms(x, y, z, pr, key, term);
         }
     }
     double mine = 0.0;  // lane k keeps sum k
@@ -255,9 +219,7 @@ int pcp_icp_batch_create(pcp_ctx* ctx, const pcp_index* target, const float* q_d
     if (nq >= (int64_t)1 << 31) return set_error(ctx, PCP_ERR_ARG, "pcp_icp_batch_create supports < 2^31 queries");
     if (target->is_f64 || target->is_h16)
         return set_error(ctx, PCP_ERR_ARG, "ICP target must be an fp32 index");
-    if (q_stride == 0) q_stride = 3 * sizeof(float);
-    if (q_stride % sizeof(float) || q_stride < 3 * sizeof(float))
-        return set_error(ctx, PCP_ERR_ARG, "strides must be whole floats, at least 3");
+    PCP_TRY(check_stride(ctx, &q_stride));
     if (seg_offsets[0] != 0 || seg_offsets[nseg] != nq)
         return set_error(ctx, PCP_ERR_ARG, "pcp_icp_batch_create: segment offsets must start at 0 and end at nq");
     for (int s = 0; s < nseg; s++)

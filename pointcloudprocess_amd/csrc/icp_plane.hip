@@ -4,7 +4,9 @@
 // the 30 accumulators of sum (n . (T q - p))^2 linearised at the pose, the scaled 6x6 LDL^T
 // solve, and the device loop around the three (with the trim of icp_trim.hip between the keys and
 // the accumulation in its trimmed form, pcp.h I3, or that trim's select over the pairs' squared
-// plane residuals between the residual and filter passes here, I3b).
+// plane residuals between this file's residual pass and that file's filter, I3b).  Owned here: the
+// table build, the kernels' loops over the keys, and the host entry points.  The per-pair
+// arithmetic and the block reductions are icp_pair.hpp's, the solve icp_plane_solve.hpp's.
 //
 // The accumulation's cost is its gather: one 32-byte record per pair at a data-dependent index,
 // both halves in one 64-byte line (two arrays would cost two lines).  Everything else streams.
@@ -12,15 +14,13 @@
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
-#include "icp_plane_solve.hpp"
+#include "icp_pair.hpp"
 
 namespace pcp {
 namespace {
 
-constexpr int kPB = 256;
+constexpr int kPB = kPairBlock;
 constexpr int kPBlocks = 2048;  // grid cap of the grid-stride kernels (pcp_icp_accumulate_owned's)
-constexpr uint64_t kNoKey = 0x7fffffffffffffffull;
 
 // one record per target point at its caller index; counts[block] = valid records it wrote
 __global__ void __launch_bounds__(kPB) k_planes_build(const float* xyz, size_t ts, const float* nrm, size_t ns,
@@ -41,165 +41,60 @@ __global__ void __launch_bounds__(kPB) k_planes_build(const float* xyz, size_t t
         rec[2 * i] = a;
         rec[2 * i + 1] = b;
     }
-    __shared__ uint32_t sm[kPB / 64];
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kPB / 64; w++) t += sm[w];
-        counts[blockIdx.x] = t;
-    }
+    const uint32_t t = block_count(cnt);
+    if (threadIdx.x == 0) counts[blockIdx.x] = t;
 }
 
 // Block partials of the 30 accumulators (pcp.h): grid-stride over the queries in their original
-// order, per-lane fp64 sums, one wave reduction, one LDS reduction.  The pose is the device 4x4
-// cast to fp32 and applied by k_acc_owned's fmaf chain; products of widened fp32 values and the
-// differences are plain fp64 operations (no contraction), so negating n negates c and r exactly
-// and every accumulated term is unchanged.
+// order, per-lane fp64 sums of plane_terms (icp_pair.hpp) over the usable pairs (plane_pair) at
+// the query's image under pose32 of the device 4x4, then block_partials.
 __global__ void __launch_bounds__(kPB) k_acc_plane(const double* T, const float* q, size_t qs, int64_t n,
                                                    const uint64_t* keys, const float4* rec, uint64_t nrec,
                                                    double* partials) {
-    float R[9], t[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) R[3 * r + c] = (float)T[4 * r + c];
-        t[r] = (float)T[4 * r + 3];
-    }
+    const Pose32 P = pose32(T);
     double acc[kPAcc];
 #pragma unroll
     for (int k = 0; k < kPAcc; k++) acc[k] = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const uint64_t key = keys[i];
-        const uint64_t j = key & 0xffffffffull;
-        if (key == kNoKey || j >= nrec) continue;
-        const float4 pn = rec[2 * j + 1];
-        if (!plane_valid(pn.x, pn.y, pn.z)) continue;
-        const float4 pp = rec[2 * j];
-        const float* qp = q + (size_t)i * qs;
-        const float x = __fmaf_rn(R[2], qp[2], __fmaf_rn(R[1], qp[1], __fmaf_rn(R[0], qp[0], t[0])));
-        const float y = __fmaf_rn(R[5], qp[2], __fmaf_rn(R[4], qp[1], __fmaf_rn(R[3], qp[0], t[1])));
-        const float z = __fmaf_rn(R[8], qp[2], __fmaf_rn(R[7], qp[1], __fmaf_rn(R[6], qp[0], t[2])));
-        const double qx = x, qy = y, qz = z, nx = pn.x, ny = pn.y, nz = pn.z;
-        double J[6];
-        J[0] = qy * nz - qz * ny;
-        J[1] = qz * nx - qx * nz;
-        J[2] = qx * ny - qy * nx;
-        J[3] = nx; J[4] = ny; J[5] = nz;
-        const double r = (nx * (qx - (double)pp.x) + ny * (qy - (double)pp.y)) + nz * (qz - (double)pp.z);
-        acc[0] += 1.0;
-        int k = 1;
+        PlanePair pr;
+        if (!plane_pair(key, rec, nrec, pr)) continue;
+        float x, y, z;
+        xform(P, q + (size_t)i * qs, x, y, z);
+        double term[kPAcc];
+        plane_terms(x, y, z, pr, key, term);
 #pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int b = a; b < 6; b++) acc[k++] += J[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; a++) acc[22 + a] += r * J[a];
-        acc[28] += r * r;
-        acc[29] += (double)__uint_as_float((uint32_t)(key >> 32));
+        for (int k = 0; k < kPAcc; k++) acc[k] += term[k];
     }
-    __shared__ double sm[kPB / 64][kPAcc];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kPAcc; k++) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) sm[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kPAcc) {
-        double v = 0.0;
-        for (int w = 0; w < kPB / 64; w++) v += sm[w][threadIdx.x];
-        partials[(int64_t)blockIdx.x * kPAcc + threadIdx.x] = v;
-    }
+    block_partials(acc, partials + (int64_t)blockIdx.x * kPAcc);
 }
 
 // Residual pass of the trim by plane residual (pcp.h, I3b): per pair the key the select of
 // icp_trim.hip ranks, (bits of (float)(r * r) << 32) | target index for a usable pair and the "no
-// pair" key otherwise.  The pose, the fmaf chain, the record test and r are k_acc_plane's, in its
-// operation order, so r is the value the accumulation squares; r -> -r under a negated normal, and
-// r * r is then the same product.
+// pair" key otherwise.  The pose, the image, the usable-pair test and r are pose32, xform,
+// plane_pair and plane_residual, which plane_terms squares: r is the value the accumulation
+// squares; r -> -r under a negated normal, and r * r is then the same product.
 __global__ void __launch_bounds__(kPB) k_res_keys(const double* T, const float* q, size_t qs, int64_t n,
                                                   const uint64_t* keys, const float4* rec, uint64_t nrec,
                                                   uint64_t* rkeys) {
-    float R[9], t[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) R[3 * r + c] = (float)T[4 * r + c];
-        t[r] = (float)T[4 * r + 3];
-    }
+    const Pose32 P = pose32(T);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const uint64_t key = keys[i];
-        const uint64_t j = key & 0xffffffffull;
         uint64_t out = kNoKey;
-        if (key != kNoKey && j < nrec) {
-            const float4 pn = rec[2 * j + 1];
-            if (plane_valid(pn.x, pn.y, pn.z)) {
-                const float4 pp = rec[2 * j];
-                const float* qp = q + (size_t)i * qs;
-                const float x = __fmaf_rn(R[2], qp[2], __fmaf_rn(R[1], qp[1], __fmaf_rn(R[0], qp[0], t[0])));
-                const float y = __fmaf_rn(R[5], qp[2], __fmaf_rn(R[4], qp[1], __fmaf_rn(R[3], qp[0], t[1])));
-                const float z = __fmaf_rn(R[8], qp[2], __fmaf_rn(R[7], qp[1], __fmaf_rn(R[6], qp[0], t[2])));
-                const double qx = x, qy = y, qz = z, nx = pn.x, ny = pn.y, nz = pn.z;
-                const double r = (nx * (qx - (double)pp.x) + ny * (qy - (double)pp.y)) + nz * (qz - (double)pp.z);
-                const float rho = (float)(r * r);
-                if (rho == rho) out = ((uint64_t)__float_as_uint(rho) << 32) | j;
-            }
+        PlanePair pr;
+        if (plane_pair(key, rec, nrec, pr)) {
+            float x, y, z;
+            xform(P, q + (size_t)i * qs, x, y, z);
+            const double r = plane_residual(x, y, z, pr);
+            const float rho = (float)(r * r);
+            if (rho == rho) out = key_make(rho, key_index(key));
         }
         rkeys[i] = out;
     }
 }
 
-// Filter and merge in one pass: k_trim_filter's keep rule read from the residual keys (usable and
-// as_float(high word) <= the select's cut), its count added to trim[1], and the result applied to
-// the caller's keys: a kept key is the caller's, all 64 bits.  In place only the rejected keys
-// are stored.
-__global__ void __launch_bounds__(kPB) k_res_filter(const uint64_t* keys, const uint64_t* rkeys, int64_t n,
-                                                    uint64_t* out, int inplace, uint64_t* trim) {
-    const float cut = __uint_as_float((uint32_t)trim[3]);
-    uint32_t cnt = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t rk = rkeys[i];
-        const bool keep = rk != kNoKey && __uint_as_float((uint32_t)(rk >> 32)) <= cut;
-        cnt += keep ? 1u : 0u;
-        if (inplace) {
-            if (!keep) out[i] = kNoKey;
-        } else {
-            out[i] = keep ? keys[i] : kNoKey;
-        }
-    }
-    __shared__ uint32_t sm[kPB / 64];
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kPB / 64; w++) t += sm[w];
-        if (t) atomicAdd((unsigned long long*)&trim[1], (unsigned long long)t);
-    }
-}
-
-// one block: out[k] = sum over the nb block partials, in a fixed order (out may be LDS)
-__device__ void sum_partials(const double* part, int nb, double* out) {
-    __shared__ double s[kPB];
-    for (int k = 0; k < kPAcc; k++) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nb; b += kPB) v += part[(int64_t)b * kPAcc + k];
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = kPB / 2; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[k] = s[0];
-        __syncthreads();
-    }
-}
-
 __global__ void __launch_bounds__(kPB) k_plane_sum(const double* part, int nb, double* out) {
-    sum_partials(part, nb, out);
+    sum_partials<kPAcc>(part, nb, out);
 }
 
 __global__ void k_plane_solve_dev(const double* acc, double* T, double* stats) {
@@ -211,7 +106,7 @@ __global__ void k_plane_solve_dev(const double* acc, double* T, double* stats) {
 // the loop's tail in one single-block launch: reduce the block partials, then thread 0 solves
 __global__ void __launch_bounds__(kPB) k_plane_sum_solve(const double* part, int nb, double* T, double* stats) {
     __shared__ double acc[kPAcc];
-    sum_partials(part, nb, acc);  // ends with a barrier: acc is visible to thread 0
+    sum_partials<kPAcc>(part, nb, acc);  // ends with a barrier: acc is visible to thread 0
     if (threadIdx.x == 0) {
         double a[kPAcc];
         for (int k = 0; k < kPAcc; k++) a[k] = acc[k];
@@ -220,13 +115,6 @@ __global__ void __launch_bounds__(kPB) k_plane_sum_solve(const double* part, int
 }
 
 int acc_blocks(int64_t nq) { return (int)std::min<int64_t>(std::max<int64_t>(1, (nq + kPB - 1) / kPB), kPBlocks); }
-
-int check_stride(pcp_ctx* ctx, size_t* stride) {
-    if (*stride == 0) *stride = 3 * sizeof(float);
-    if (*stride % sizeof(float) || *stride < 3 * sizeof(float))
-        return set_error(ctx, PCP_ERR_ARG, "strides must be whole floats, at least 3");
-    return PCP_OK;
-}
 
 void launch_acc(pcp_ctx* ctx, const double* T_dev, const float* q, size_t q_stride, int64_t nq, const uint64_t* keys,
                 const pcp_icp_planes* pl, int nb, double* part) {
@@ -244,11 +132,7 @@ int trim_plane_async(pcp_ctx* ctx, const double* T_dev, const float* q, size_t q
         hipLaunchKernelGGL(k_res_keys, dim3(nb), dim3(kPB), 0, ctx->stream, T_dev, q, q_stride / sizeof(float), n,
                            keys, (const float4*)pl->rec, (uint64_t)pl->n, rkeys);
     PCP_TRY(trim_select_async(ctx, rkeys, n, frac, mult, d_floor, trim, work));
-    if (n > 0)
-        hipLaunchKernelGGL(k_res_filter, dim3(nb), dim3(kPB), 0, ctx->stream, keys, (const uint64_t*)rkeys, n, out,
-                           out == keys ? 1 : 0, trim);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
+    return trim_filter_async(ctx, keys, rkeys, n, out, trim);
 }
 
 // iters x (keys, [trim in place: trim = {frac, mult, d_floor}, by the point distance (I3) or, with

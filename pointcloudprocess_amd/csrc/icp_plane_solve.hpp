@@ -1,5 +1,6 @@
-// The point-to-plane minimisation's per-pair record test and its 6x6 solve (pcp.h I2), shared by
-// the single-pair loop (icp_plane.hip) and the batched one (icp_batch.hip): one arithmetic.
+// The point-to-plane minimisation's plane table, the validity test of a record's normal and the
+// 6x6 solve (pcp.h I2), shared by the single-pair loop (icp_plane.hip) and the batched one
+// (icp_batch.hip): one arithmetic.  What is computed per pair is icp_pair.hpp's.
 #pragma once
 #include <cmath>
 

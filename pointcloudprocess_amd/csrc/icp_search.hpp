@@ -1,7 +1,8 @@
 // The ICP correspondence contract's device arithmetic, shared by the single-pair kernels (icp.hip)
 // and the batched ones (icp_batch.hip) so that both paths run one set of expressions: the fp32
-// pose chain, the fp32 d2, the running (d2, target index) winner and the exact row search over the
-// fp32 grid index, plus the cell key both query sorts order by.
+// pose chain (every kernel that needs a query's image under the pose calls xform), the fp32 d2,
+// the running (d2, target index) winner and the exact row search over the fp32 grid index, plus
+// the cell key both query sorts order by.  What is done with a found pair is icp_pair.hpp's.
 #pragma once
 #include "grid.hpp"
 
@@ -14,6 +15,11 @@ __device__ __forceinline__ void xform(const A& a, const float4 q, float& x, floa
     x = __fmaf_rn(a.R[2], q.z, __fmaf_rn(a.R[1], q.y, __fmaf_rn(a.R[0], q.x, a.t[0])));
     y = __fmaf_rn(a.R[5], q.z, __fmaf_rn(a.R[4], q.y, __fmaf_rn(a.R[3], q.x, a.t[1])));
     z = __fmaf_rn(a.R[8], q.z, __fmaf_rn(a.R[7], q.y, __fmaf_rn(a.R[6], q.x, a.t[2])));
+}
+// the same chain for a query read from a caller's strided float array
+template <typename A>
+__device__ __forceinline__ void xform(const A& a, const float* q, float& x, float& y, float& z) {
+    xform(a, make_float4(q[0], q[1], q[2], 0.f), x, y, z);
 }
 
 // running 1-NN: best d2, its target index (tie order) and its position in the scanned array

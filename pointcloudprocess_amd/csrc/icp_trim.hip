@@ -13,21 +13,24 @@
 // peels up to kPeel groups first: the lanes that share the first active lane's digit are counted
 // with a ballot and added by one lane.  What is still active after kPeel rounds (digits spread
 // over many bins, where collisions are rare) adds one by one.
+//
+// Owned here: the select and the one filter kernel, for both trims: the point trim ranks the keys
+// themselves, the trim by plane residual (icp_plane.hip) ranks its residual keys and filters the
+// caller's keys by them.  The key's layout and the block count are icp_pair.hpp's.
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "icp_pair.hpp"
 
 namespace pcp {
 namespace {
 
-constexpr int kTB = 256;
+constexpr int kTB = kPairBlock;
 constexpr int kTPer = 4;             // keys per thread and block iteration of the histogram passes
 constexpr int kTHistBlocks = 1024;   // grid cap of the histogram passes (4 blocks of 8 KB LDS per CU)
 constexpr int kTFilterBlocks = 2048; // grid cap of the filter
 constexpr int kPeel = 4;
 constexpr int kTBins = 2048;         // bins of the widest digit
-constexpr uint64_t kNoKey = 0x7fffffffffffffffull;
 
 __host__ __device__ constexpr int digit_bits(int p) { return p == 2 ? 10 : 11; }
 __host__ __device__ constexpr int digit_shift(int p) { return p == 0 ? 21 : p == 1 ? 10 : 0; }
@@ -47,7 +50,7 @@ __device__ __forceinline__ TrimState* state_of(uint32_t* work) { return (TrimSta
 template <int P>
 __device__ __forceinline__ void count_digit(uint32_t* h, uint64_t key, uint32_t prefix) {
     constexpr int shift = digit_shift(P), bits = digit_bits(P);
-    const uint32_t b = (uint32_t)(key >> 32);
+    const uint32_t b = key_d2_bits(key);
     bool act = key != kNoKey;
     if constexpr (P > 0) act = act && (b >> (shift + bits)) == prefix;
     const uint32_t d = (b >> shift) & ((1u << bits) - 1u);
@@ -172,31 +175,30 @@ __global__ void k_trim_empty(float d_floor, uint64_t* trim) {
     trim[3] = __float_as_uint(d_floor * d_floor);
 }
 
-// keep a valid key iff as_float(b) <= cut; in place only the rejected keys are stored
-__global__ void __launch_bounds__(kTB) k_trim_filter(const uint64_t* keys, int64_t n, uint64_t* out, int inplace,
-                                                     uint64_t* trim) {
+// The filter: pair i is kept iff its ranked key is valid and as_float(its high word) <= cut; the
+// kept count is added to trim[1].  RES = false ranks the keys themselves (pcp.h I3); in place only
+// the rejected valid keys are stored.  RES = true ranks the residual keys rkeys of icp_plane.hip's
+// k_res_keys (I3b) and applies the result to the caller's keys: a kept key is the caller's, all 64
+// bits, and in place every key not kept is stored, since a pair without a usable plane record is
+// still a pair in keys.
+template <bool RES>
+__global__ void __launch_bounds__(kTB) k_trim_filter(const uint64_t* keys, const uint64_t* rkeys, int64_t n,
+                                                     uint64_t* out, int inplace, uint64_t* trim) {
     const float cut = __uint_as_float((uint32_t)trim[3]);
     uint32_t cnt = 0;
     for (int64_t i = blockIdx.x * (int64_t)kTB + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTB) {
-        const uint64_t key = keys[i];
-        const bool valid = key != kNoKey;
-        const bool keep = valid && __uint_as_float((uint32_t)(key >> 32)) <= cut;
+        const uint64_t rk = RES ? rkeys[i] : keys[i];
+        const bool valid = rk != kNoKey;
+        const bool keep = valid && key_d2(rk) <= cut;
         cnt += keep ? 1u : 0u;
         if (inplace) {
-            if (valid && !keep) out[i] = kNoKey;
+            if (RES ? !keep : valid && !keep) out[i] = kNoKey;
         } else {
-            out[i] = keep ? key : kNoKey;
+            out[i] = keep ? (RES ? keys[i] : rk) : kNoKey;
         }
     }
-    __shared__ uint32_t sm[kTB / 64];
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kTB / 64; w++) t += sm[w];
-        if (t) atomicAdd((unsigned long long*)&trim[1], (unsigned long long)t);
-    }
+    const uint32_t t = block_count(cnt);
+    if (threadIdx.x == 0 && t) atomicAdd((unsigned long long*)&trim[1], (unsigned long long)t);
 }
 
 template <int P>
@@ -231,14 +233,23 @@ int trim_select_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac,
     return PCP_OK;
 }
 
+int trim_filter_async(pcp_ctx* ctx, const uint64_t* keys, const uint64_t* rkeys, int64_t n, uint64_t* out,
+                      uint64_t* trim) {
+    if (n == 0) return PCP_OK;
+    const dim3 grid(grid_for(n, kTB, kTFilterBlocks));
+    const int inplace = out == keys ? 1 : 0;
+    if (rkeys)
+        hipLaunchKernelGGL(k_trim_filter<true>, grid, dim3(kTB), 0, ctx->stream, keys, rkeys, n, out, inplace, trim);
+    else
+        hipLaunchKernelGGL(k_trim_filter<false>, grid, dim3(kTB), 0, ctx->stream, keys, rkeys, n, out, inplace, trim);
+    PCP_LAUNCH_CHECK(ctx);
+    return PCP_OK;
+}
+
 int trim_keys_async(pcp_ctx* ctx, const uint64_t* keys, int64_t n, float frac, float mult, float d_floor,
                     uint64_t* out, uint64_t* trim, uint32_t* work) {
     PCP_TRY(trim_select_async(ctx, keys, n, frac, mult, d_floor, trim, work));
-    if (n == 0) return PCP_OK;
-    hipLaunchKernelGGL(k_trim_filter, dim3(grid_for(n, kTB, kTFilterBlocks)), dim3(kTB), 0, ctx->stream, keys, n, out,
-                       out == keys ? 1 : 0, trim);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
+    return trim_filter_async(ctx, keys, nullptr, n, out, trim);
 }
 
 }  // namespace pcp
