@@ -609,14 +609,15 @@ int build_impl(pcp_ctx* ctx, const T* xyz, size_t stride, int64_t n_in, const in
         if (g.dense && is_f64)
             hipLaunchKernelGGL(k_brick_flag, dim3(grid_for(g.nbricks, kB)), dim3(kB), 0, st, ix->brick, g.nbricks);
         // ---- chunk boundaries of the sorted keys
-        const int64_t nchunk = (ncells + 1 + kChunk - 1) / kChunk;
+        // (cells [0, ncells + 1]: the pad entry is written too, = n like the closing entry)
+        const int64_t nchunk = (ncells + 2 + kChunk - 1) / kChunk;
         uint32_t* lo = nullptr;
         PCP_TRY(tmp.get(&lo, nchunk + 1));
         hipLaunchKernelGGL(k_chunk_lo, dim3(grid_for(n + 1, kB, kScanBlocks)), dim3(kB), 0, st, (const uint32_t*)key1, n,
                            nchunk, lo);
         // ---- cell starts straight from the sorted keys (no count array, no scan)
         hipLaunchKernelGGL(k_cell_starts, dim3((unsigned)nchunk), dim3(kB), 0, st, (const uint32_t*)key1,
-                           (const uint32_t*)lo, ncells + 1, count);
+                           (const uint32_t*)lo, ncells + 2, count);
         tmp.free(lo);
         g.cstart = count;
         if (g.dense && is_f64 && n > 0)

@@ -654,9 +654,10 @@ struct Top3P {
         t1 = umed3(t0, t1, x);
         t0 = min(t0, x);
     }
-    // the wave's lists with a uniform trip count (lanes past their own list read the far
-    // sentinel: d2 = inf, never kept), U loads per step, the next step's loads issued before
-    // this step's keys are formed (software pipeline: two batches in flight).  With G lanes per
+    // the wave's lists with a uniform trip count Lg = ceil(longest list / G), rounded up to whole
+    // batches of U loads and no further (lanes past their own list read the far sentinel: d2 = inf,
+    // never kept), the next batch's loads issued before this batch's keys are formed (software
+    // pipeline: two batches in flight wherever a next batch exists).  With G lanes per
     // query, lane `sub` of the group takes list entries sub, sub + G, sub + 2G, ...: the group's
     // loads of one step are G consecutive records of a row (one or two cache lines), so a wave
     // instruction touches ~64 / G lines instead of 64 (what bounds the sparse search lists).
@@ -672,29 +673,43 @@ struct Top3P {
         auto lv = [=](uint32_t v) { return v * G + sub; };  // this lane's v-th list entry
         auto addr = [=](uint32_t v) { return cat_addr_l(lv(v), c1, c2, c3, L, o0, o1, o2, o3, sent); };
         const uint32_t Lg = (Lw + G - 1) / G;
+        if (Lg == 0) return;  // a chunk of empty lists loads nothing
         constexpr int U = 4;
         float4 A[U], B[U];
+        auto load = [&](float4 (&R)[U], uint32_t v) {
 #pragma unroll
-        for (int u = 0; u < U; u++) A[u] = ld16(pts, addr(u));
-        for (uint32_t v = 0; v < Lg; v += 2 * U) {
-            // two register sets, no copies: B's loads are in flight while A's keys are formed
+            for (int u = 0; u < U; u++) R[u] = ld16(pts, addr(v + u));
+        };
+        auto rank = [&](const float4 (&R)[U], uint32_t v) {
 #pragma unroll
-            for (int u = 0; u < U; u++) B[u] = ld16(pts, addr(v + U + u));
+            for (int u = 0; u < U; u++) {
+                consider(qx, qy, qz, R[u], lv(v + u));
+                if constexpr (LOOK) m2->consider(tx, ty, tz, R[u], lv(v + u));
+            }
+        };
+        // two register sets, no copies: the next batch's loads are in flight while this batch's
+        // keys are formed.  No batch is issued at or past Lg (Lg is wave-uniform: scalar
+        // branches).  The loop has one exit and runs only while both of its batches exist; the last
+        // one or two batches are ranked on paths of their own, so the wait before a ranking counts
+        // the same loads in flight on every path into it.  (A load skipped under a branch that
+        // joins before the ranking makes that wait a full one: the join takes the stricter count.)
+        load(A, 0);
+        uint32_t v = 0;
+        for (; v + 2 * U < Lg; v += 2 * U) {  // batches v + U and v + 2U both exist
+            load(B, v + U);
             __builtin_amdgcn_sched_barrier(0);  // keep B's loads ahead of A's keys
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                consider(qx, qy, qz, A[u], lv(v + u));
-                if constexpr (LOOK) m2->consider(tx, ty, tz, A[u], lv(v + u));
-            }
-            if (v + U >= Lg) break;
-#pragma unroll
-            for (int u = 0; u < U; u++) A[u] = ld16(pts, addr(v + 2 * U + u));
+            rank(A, v);
+            load(A, v + 2 * U);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                consider(qx, qy, qz, B[u], lv(v + U + u));
-                if constexpr (LOOK) m2->consider(tx, ty, tz, B[u], lv(v + U + u));
-            }
+            rank(B, v + U);
+        }
+        if (v + U < Lg) {  // two batches left
+            load(B, v + U);
+            __builtin_amdgcn_sched_barrier(0);
+            rank(A, v);
+            rank(B, v + U);
+        } else {
+            rank(A, v);
         }
     }
     // the G lanes of a query merge their 4 smallest keys: per butterfly step the 4 smallest of
