@@ -663,9 +663,9 @@ int pcp_get_rot_icp_plane_rtrimmed(pcp_ctx* ctx, const void* src_aos48_dev, int6
  *   whatever nseg is, and poses bit-identical to calling the three entries in turn.  The plane
  *   table's size must be the target index's caller size (PCP_ERR_ARG otherwise).
  *
- * Not here: the point-to-point minimisation, and the trimmed loops of I3 / I3b.  pcp_icp_trim_keys
- * over a batch's keys takes ONE quantile across all segments, not one per segment; a segmented
- * select is future work. */
+ * Not here: the point-to-point minimisation.  The trims of I3 / I3b per segment, and the trimmed
+ * loops, are I5b below; pcp_icp_trim_keys itself over a batch's keys takes ONE quantile across all
+ * segments, not one per segment. */
 typedef struct pcp_icp_batch pcp_icp_batch;
 int pcp_icp_batch_create(pcp_ctx* ctx, const pcp_index* target, const float* q_dev, size_t q_stride_bytes,
                          int64_t nq, const int64_t* seg_offsets_host /* nseg + 1 */, int nseg,
@@ -682,6 +682,82 @@ int pcp_icp_batch_solve_plane_dev(pcp_ctx* ctx, const double* acc_dev, int nseg,
                                   double* stats_dev /* nseg x 4 */);
 int pcp_icp_batch_run_plane_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const pcp_icp_planes* planes, double* T_dev,
                                 float rmax, int iters, double* stats_dev /* nseg x 4, zeroed by the caller */);
+
+/* ----------------------------------------------------------------------- I5b: per-segment trims of a batch
+ * The trims of I3 and I3b applied to every segment of a pcp_icp_batch separately: one exact order
+ * statistic, one cut and one kept count PER SEGMENT, in a fixed number of launches whatever nseg and
+ * the segment sizes are.  Frames that overlap the map only in part, each at its own distance from
+ * convergence, need their own quantile; one pooled quantile over all keys is wrong for them.  With
+ * off = the seg_offsets passed to pcp_icp_batch_create:
+ *
+ * Per segment, bit for bit.  For every segment s the output keys [off[s], off[s + 1]) and row s of
+ *   trim_dev (nseg x 4: {m, kept, sel, bits of cut}) are exactly what the single entry writes for
+ *   that slice alone:
+ *     pcp_icp_batch_trim_keys: pcp_icp_trim_keys(keys_dev + off[s], n_s, frac, mult, d_floor, ..);
+ *     pcp_icp_batch_trim_keys_plane: pcp_icp_trim_keys_plane over that slice of keys, segment s's
+ *       queries and the pose T_dev + 16 s.
+ *   The valid (I3) and usable (I3b) rules, r = (uint64) floor((double)frac * (double)(m - 1)) on
+ *   the device in fp64, sel = the exact r-th smallest b_i of the segment counted from 0 with
+ *   multiplicity (0 when m == 0), the fp32 cut m2 = mult * mult, c = m2 * as_float(sel),
+ *   f2 = d_floor * d_floor, cut = f2 when c is NaN, else max(c, f2), and keep iff as_float(b_i) <= cut
+ *   are those sections' word for word.  A kept key is unchanged in all 64 bits; every other written
+ *   key is exactly INT64_MAX.
+ * Queries.  The plane trim reads the handle's own copy of the queries (pcp_icp_batch_create copies
+ *   them, a non-finite query included: its rho is NaN, so its pair is not usable).  keys_dev is nq
+ *   keys in the ORIGINAL query order, as pcp_icp_batch_keys_dev writes them.
+ * Shared parameters.  frac, mult and d_floor are one scalar each, shared by all segments.
+ * Empty and invalid segments.  An empty segment writes the row {0, 0, 0, bits(f2)}.  A segment
+ *   whose keys are all invalid (I3) or unusable (I3b) writes {0, 0, 0, bits(f2)} and every key of it
+ *   is INT64_MAX afterwards.  nseg == 0 writes nothing and returns PCP_OK.
+ * Aliasing.  keys_out_dev == keys_dev (in place) is allowed: the point trim then stores only the
+ *   rejected valid keys, the plane trim every key not kept (a pair without a usable plane record is
+ *   still a pair in keys).  Out of place every one of the nq keys is written.  Any other overlap
+ *   is the caller's error.
+ * Composition.  pcp_icp_batch_accumulate_plane(keys_out)[s][0] == kept[s] for the plane trim.
+ * Arguments.  PCP_ERR_ARG for: a null context or batch; a null trim_dev with nseg > 0, and for the
+ *   plane trim a null T_dev or planes with nseg > 0; null key pointers with nq > 0; frac outside
+ *   [0, 1] or NaN; mult or d_floor negative or not finite.  The loops add: iters < 0, !(rmax >= 0),
+ *   a null stats_dev with nseg > 0, and a plane table whose size is not the target index's caller
+ *   size.  A rejected call writes nothing.
+ * Execution.  Asynchronous on the context's stream, no host synchronisation.  Three launches: a
+ *   statistic pass (one 64-query chunk per wave) that writes, per slot of the handle's padded
+ *   layout, (b_i << 32 | low word of the key) for a valid / usable pair and INT64_MAX otherwise;
+ *   one workgroup per segment that runs I3's radix select (digits of 11, 11 and 10 bits) over its
+ *   own slots with the histogram and the state in shared memory, and writes the segment's row; a
+ *   filter pass (one chunk per wave) that keeps or rejects key i and adds the kept count to its row
+ *   with an integer atomic.  Counting is integer only and there are no float atomics: the result
+ *   is bit for bit the same on every run.  The handle still owns exactly three allocator blocks;
+ *   the 64-bit statistic per slot is per-call guard memory, so pcp_ctx_alloc_stats balances on every
+ *   path, error paths included.  A segment is selected by ONE workgroup: the single handle with
+ *   pcp_icp_trim_keys stays the path for one very large query set.
+ *
+ * pcp_icp_batch_run_plane_trimmed_dev / _rtrimmed_dev = iters x (pcp_icp_batch_keys_dev, the point /
+ *   plane trim in place at the iteration's poses, pcp_icp_batch_accumulate_plane, sum + solve) over
+ *   all segments, with no host round trip and no allocation inside the loop: SIX launches per
+ *   iteration (search, statistic, select, filter, accumulate, sum + solve) whatever nseg and the
+ *   segment sizes are.  Poses and stats are bit-identical to calling the four entries in turn.
+ *   stats_dev as pcp_icp_batch_run_plane_dev (nseg x 4, zeroed by the caller); trim_dev receives
+ *   the rows of the last iteration's trim and is untouched when iters == 0.  rmax stays the search
+ *   bound.  A segment left with fewer than 6 pairs fails its solve and freezes: that segment only,
+ *   the others carry on, and a frozen segment is still trimmed every iteration.
+ *
+ * Not here: per-segment frac, mult or d_floor; a select split over several workgroups for one very
+ * large segment; the point-to-point minimisation; pcp_get_rot_icp_*-style wrappers. */
+int pcp_icp_batch_trim_keys(pcp_ctx* ctx, pcp_icp_batch* batch, const uint64_t* keys_dev /* nq, ORIGINAL order */,
+                            float frac, float mult, float d_floor,
+                            uint64_t* keys_out_dev, uint64_t* trim_dev /* nseg x 4 */);
+int pcp_icp_batch_trim_keys_plane(pcp_ctx* ctx, pcp_icp_batch* batch, const double* T_dev /* nseg x 16 */,
+                                  const uint64_t* keys_dev, const pcp_icp_planes* planes,
+                                  float frac, float mult, float d_floor,
+                                  uint64_t* keys_out_dev, uint64_t* trim_dev /* nseg x 4 */);
+int pcp_icp_batch_run_plane_trimmed_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const pcp_icp_planes* planes,
+                                        double* T_dev, float rmax, float frac, float mult, float d_floor,
+                                        int iters, double* stats_dev /* nseg x 4 */,
+                                        uint64_t* trim_dev /* nseg x 4: last iteration */);
+int pcp_icp_batch_run_plane_rtrimmed_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const pcp_icp_planes* planes,
+                                         double* T_dev, float rmax, float frac, float mult, float d_floor,
+                                         int iters, double* stats_dev /* nseg x 4 */,
+                                         uint64_t* trim_dev /* nseg x 4: last iteration */);
 
 /* ----------------------------------------------------------------------- I4: pose lines
  * Host-only (no device work): n frames' poses as row-major 4x4 doubles, rots[16 * i].

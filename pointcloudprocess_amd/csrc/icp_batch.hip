@@ -18,24 +18,11 @@
 
 #include "sortcfg.hpp"
 
-#include "icp_pair.hpp"
-
-struct pcp_icp_batch {
-    pcp_ctx* owner = nullptr;         // the creating context: owns the buffers (a lifetime reference)
-    const pcp_index* target = nullptr;  // borrowed
-    int64_t nq = 0;                   // queries passed to pcp_icp_batch_create
-    int nseg = 0;
-    int64_t nch = 0;                  // 64-query chunks of the padded sorted layout
-    float4* rec = nullptr;            // 64 * nch: {x, y, z, bits(original index)}; a pad slot has index -1
-    int32_t* chunk_seg = nullptr;     // nch: the segment of a chunk
-    int32_t* seg_chunk = nullptr;     // nseg + 1: the first chunk of a segment
-};
+#include "icp_batch.hpp"
 
 namespace pcp {
 namespace {
 
-constexpr int kBB = 256;          // 4 waves = 4 chunks per block
-constexpr int kBW = kBB / 64;
 constexpr int kSumGroups = 8;     // k_batch_sum_solve: chunk c of a segment is summed by group c % 8
 
 // ---- create: sort key (segment, cell key at the identity) and the caller index as payload
@@ -176,23 +163,28 @@ __global__ void __launch_bounds__(64) k_batch_solve(const double* acc, int nseg,
     solve_apply(a, T + 16 * (int64_t)s, stats + 4 * (int64_t)s);
 }
 
-unsigned chunk_grid(int64_t nch) { return (unsigned)((nch + kBW - 1) / kBW); }
+}  // namespace
 
-void launch_search(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, float rmax, uint64_t* keys) {
+void batch_launch_search(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, float rmax, uint64_t* keys) {
     const pcp_index* tg = b->target;
     hipLaunchKernelGGL(k_batch_search, dim3(chunk_grid(b->nch)), dim3(kBB), 0, ctx->stream, tg->g,
                        (const float4*)tg->pts, (const float4*)b->rec, (const int32_t*)b->chunk_seg, b->nch, T_dev,
                        rmax * rmax, search_margin(tg->g), keys);
 }
 
-void launch_acc(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, const uint64_t* keys,
-                const pcp_icp_planes* pl, double* part) {
+void batch_launch_acc(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, const uint64_t* keys,
+                      const pcp_icp_planes* pl, double* part) {
     hipLaunchKernelGGL(k_batch_acc, dim3(chunk_grid(b->nch)), dim3(kBB), 0, ctx->stream, (const float4*)b->rec,
                        (const int32_t*)b->chunk_seg, b->nch, T_dev, keys, (const float4*)pl->rec, (uint64_t)pl->n,
                        part);
 }
 
-}  // namespace
+void batch_launch_sum_solve(pcp_ctx* ctx, const pcp_icp_batch* b, const double* part, double* acc_out, double* T,
+                            double* stats) {
+    hipLaunchKernelGGL(k_batch_sum_solve, dim3(b->nseg), dim3(kBB), 0, ctx->stream, part,
+                       (const int32_t*)b->seg_chunk, acc_out, T, stats);
+}
+
 }  // namespace pcp
 
 using namespace pcp;
@@ -302,7 +294,7 @@ int pcp_icp_batch_keys_dev(pcp_ctx* ctx, pcp_icp_batch* b, const double* T_dev, 
     if (!ctx || !b || !(rmax >= 0.f) || (b->nseg > 0 && !T_dev) || (b->nq > 0 && !keys_dev)) return PCP_ERR_ARG;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     if (b->nch == 0) return PCP_OK;
-    launch_search(ctx, b, T_dev, rmax, keys_dev);
+    batch_launch_search(ctx, b, T_dev, rmax, keys_dev);
     PCP_LAUNCH_CHECK(ctx);
     return PCP_OK;
 }
@@ -316,9 +308,8 @@ int pcp_icp_batch_accumulate_plane(pcp_ctx* ctx, pcp_icp_batch* b, const double*
     Tmp tmp(ctx);
     double* part = nullptr;
     PCP_TRY(tmp.get(&part, (size_t)b->nch * kPAcc));
-    if (b->nch > 0) launch_acc(ctx, b, T_dev, keys_dev, planes, part);
-    hipLaunchKernelGGL(k_batch_sum_solve, dim3(b->nseg), dim3(kBB), 0, ctx->stream, (const double*)part,
-                       (const int32_t*)b->seg_chunk, acc_dev, (double*)nullptr, (double*)nullptr);
+    if (b->nch > 0) batch_launch_acc(ctx, b, T_dev, keys_dev, planes, part);
+    batch_launch_sum_solve(ctx, b, part, acc_dev, nullptr, nullptr);
     PCP_LAUNCH_CHECK(ctx);
     return PCP_OK;
 }
@@ -349,11 +340,10 @@ int pcp_icp_batch_run_plane_dev(pcp_ctx* ctx, pcp_icp_batch* b, const pcp_icp_pl
     PCP_TRY(tmp.get(&part, (size_t)b->nch * kPAcc));
     for (int it = 0; it < iters; it++) {
         if (b->nch > 0) {
-            launch_search(ctx, b, T_dev, rmax, keys);
-            launch_acc(ctx, b, T_dev, keys, planes, part);
+            batch_launch_search(ctx, b, T_dev, rmax, keys);
+            batch_launch_acc(ctx, b, T_dev, keys, planes, part);
         }
-        hipLaunchKernelGGL(k_batch_sum_solve, dim3(b->nseg), dim3(kBB), 0, ctx->stream, (const double*)part,
-                           (const int32_t*)b->seg_chunk, (double*)nullptr, T_dev, stats_dev);
+        batch_launch_sum_solve(ctx, b, part, nullptr, T_dev, stats_dev);
     }
     PCP_LAUNCH_CHECK(ctx);
     return PCP_OK;

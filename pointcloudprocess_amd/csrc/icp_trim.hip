@@ -8,11 +8,8 @@
 // the digit holding the wanted rank and the rank left inside it.  The filter is the fourth and
 // last read.  Everything is integer counting, so the result is the same bit for bit on every run.
 //
-// ICP distances sit in a handful of exponents, so in the leading digit almost every lane of a
-// wave lands in the same few bins, and 64 same-address LDS atomics serialise.  Each wave therefore
-// peels up to kPeel groups first: the lanes that share the first active lane's digit are counted
-// with a ballot and added by one lane.  What is still active after kPeel rounds (digits spread
-// over many bins, where collisions are rare) adds one by one.
+// Same-address LDS atomics of a wave are peeled by count_digit (icp_trim.hpp), which the per-segment
+// select of icp_batch_trim.hip shares with the rank and the cut.
 //
 // Owned here: the select and the one filter kernel, for both trims: the point trim ranks the keys
 // themselves, the trim by plane residual (icp_plane.hip) ranks its residual keys and filters the
@@ -20,7 +17,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "icp_pair.hpp"
+#include "icp_trim.hpp"
 
 namespace pcp {
 namespace {
@@ -29,11 +26,6 @@ constexpr int kTB = kPairBlock;
 constexpr int kTPer = 4;             // keys per thread and block iteration of the histogram passes
 constexpr int kTHistBlocks = 1024;   // grid cap of the histogram passes (4 blocks of 8 KB LDS per CU)
 constexpr int kTFilterBlocks = 2048; // grid cap of the filter
-constexpr int kPeel = 4;
-constexpr int kTBins = 2048;         // bins of the widest digit
-
-__host__ __device__ constexpr int digit_bits(int p) { return p == 2 ? 10 : 11; }
-__host__ __device__ constexpr int digit_shift(int p) { return p == 0 ? 21 : p == 1 ? 10 : 0; }
 
 // work memory: hist[3][kTBins] u32, then the state between the passes
 struct TrimState {
@@ -45,30 +37,6 @@ struct TrimState {
 constexpr size_t kStateWord = 3 * (size_t)kTBins;  // u32 offset of the state (8-byte aligned)
 
 __device__ __forceinline__ TrimState* state_of(uint32_t* work) { return (TrimState*)(work + kStateWord); }
-
-// count one key's digit of pass P into the block's LDS histogram (called by whole waves)
-template <int P>
-__device__ __forceinline__ void count_digit(uint32_t* h, uint64_t key, uint32_t prefix) {
-    constexpr int shift = digit_shift(P), bits = digit_bits(P);
-    const uint32_t b = key_d2_bits(key);
-    bool act = key != kNoKey;
-    if constexpr (P > 0) act = act && (b >> (shift + bits)) == prefix;
-    const uint32_t d = (b >> shift) & ((1u << bits) - 1u);
-    const int lane = threadIdx.x & 63;
-    uint64_t todo = __ballot(act);
-#pragma unroll
-    for (int r = 0; r < kPeel; r++) {
-        if (todo == 0) break;  // wave-uniform
-        const int leader = __ffsll((unsigned long long)todo) - 1;
-        const uint32_t dl = (uint32_t)__builtin_amdgcn_readlane((int)d, leader);
-        const bool mine = act && d == dl;
-        const uint64_t same = __ballot(mine);
-        if (lane == leader) atomicAdd(&h[dl], (uint32_t)__popcll(same));
-        if (mine) act = false;
-        todo &= ~same;
-    }
-    if (act) atomicAdd(&h[d], 1u);
-}
 
 // pass P: histogram of digit P over the valid keys whose higher digits equal the state's prefix
 template <int P>
@@ -129,7 +97,7 @@ __global__ void __launch_bounds__(kTB) k_trim_pick(uint32_t* work, float frac, f
         if (P == 0) {
             const uint64_t m = part[kTB - 1];
             st->m = m;
-            rank = m ? (uint64_t)floor((double)frac * (double)(m - 1)) : 0;
+            rank = trim_rank(frac, m);
             old_s = 0;
         } else {
             rank = st->rank;
@@ -158,14 +126,10 @@ __global__ void __launch_bounds__(kTB) k_trim_pick(uint32_t* work, float frac, f
         st->rank = left_s;
         if (P == 2) {
             const uint32_t sel = pre_s;
-            const float m2 = mult * mult;
-            const float cc = m2 * __uint_as_float(sel);
-            const float f2 = d_floor * d_floor;
-            const float cut = (cc > f2) ? cc : f2;  // f2 when cc is NaN
             trim[0] = st->m;
             trim[1] = 0;
             trim[2] = sel;
-            trim[3] = __float_as_uint(cut);
+            trim[3] = trim_cut_bits(sel, mult, d_floor);
         }
     }
 }

@@ -607,7 +607,8 @@ class ICPBatch:
     """pcp_icp_batch (pcp.h I5): B query segments registered against one fp32 target index, one
     device pose per segment, three launches per point-to-plane iteration whatever B is.  q: (n, >= 3)
     fp32 device tensor; seg_offsets: B + 1 non-decreasing integers from 0 to n (segment s is
-    q[seg_offsets[s]:seg_offsets[s + 1]]).  Keys are in q's order."""
+    q[seg_offsets[s]:seg_offsets[s + 1]]).  Keys are in q's order.  The trimmed loops (pcp.h I5b) trim
+    every segment by its own quantile and take six launches per iteration, again whatever B is."""
 
     def __init__(self, target_index, q, seg_offsets):
         self.index = target_index
@@ -671,6 +672,60 @@ class ICPBatch:
         self._check_poses(T_dev, stats)
         ctx.check(ctx.lib.pcp_icp_batch_run_plane_dev(ctx.h, self.h, planes.h, _ptr(T_dev), float(rmax), int(iters),
                                                       _ptr(stats)))
+
+    # ---- per-segment trims (pcp.h I5b): one quantile, cut and kept count per segment
+    def _trim_io(self, keys, out):
+        out = torch.empty_like(keys) if out is None else out
+        assert keys.dtype == torch.int64 and out.dtype == torch.int64
+        assert keys.numel() >= self.nq and out.numel() >= self.nq and keys.is_contiguous() and out.is_contiguous()
+        return out, torch.zeros((self.nseg, 4), dtype=torch.int64, device=self.ctx.device)
+
+    def trim_keys(self, keys, frac, mult=1.0, d_floor=0.0, out=None):
+        """icp_trim_keys on every segment's slice of keys (q's order) separately.  out=None writes a
+        new tensor, out=keys works in place.  Returns (keys_out, trim) with trim (B, 4) int64: per
+        segment [m, kept, sel, bits of cut]."""
+        ctx = self.ctx
+        out, trim = self._trim_io(keys, out)
+        ctx.check(ctx.lib.pcp_icp_batch_trim_keys(ctx.h, self.h, _ptr(keys) if self.nq else None, float(frac),
+                                                  float(mult), float(d_floor), _ptr(out) if self.nq else None,
+                                                  _ptr(trim) if self.nseg else None))
+        return out, trim
+
+    def trim_keys_plane(self, T_dev, keys, planes, frac, mult=1.0, d_floor=0.0, out=None):
+        """icp_trim_keys_plane on every segment separately: its slice of keys, its queries (the
+        handle's copy) and its pose T_dev[s].  out and the return values as trim_keys."""
+        ctx = self.ctx
+        out, trim = self._trim_io(keys, out)
+        self._check_poses(T_dev)
+        ctx.check(ctx.lib.pcp_icp_batch_trim_keys_plane(ctx.h, self.h, _ptr(T_dev), _ptr(keys) if self.nq else None,
+                                                        planes.h, float(frac), float(mult), float(d_floor),
+                                                        _ptr(out) if self.nq else None,
+                                                        _ptr(trim) if self.nseg else None))
+        return out, trim
+
+    def _run_trimmed(self, fn, planes, T_dev, stats, rmax, frac, mult, d_floor, iters, trim):
+        ctx = self.ctx
+        self._check_poses(T_dev, stats)
+        trim = torch.zeros((self.nseg, 4), dtype=torch.int64, device=ctx.device) if trim is None else trim
+        assert trim.dtype == torch.int64 and trim.numel() >= 4 * self.nseg and trim.is_contiguous()
+        ctx.check(fn(ctx.h, self.h, planes.h, _ptr(T_dev), float(rmax), float(frac), float(mult), float(d_floor),
+                     int(iters), _ptr(stats), _ptr(trim) if self.nseg else None))
+        return trim
+
+    def run_plane_trimmed_dev(self, planes, T_dev, stats, rmax, frac, mult=1.0, d_floor=0.0, iters=4, trim=None):
+        """run_plane_dev with trim_keys(frac, mult, d_floor) in place between the keys and the
+        accumulation of every iteration: six launches per iteration whatever B and the segment sizes
+        are.  A segment left with fewer than 6 pairs freezes alone.  Returns trim: the last
+        iteration's (B, 4) rows [m, kept, sel, bits of cut] (int64 device tensor)."""
+        return self._run_trimmed(self.ctx.lib.pcp_icp_batch_run_plane_trimmed_dev, planes, T_dev, stats, rmax, frac,
+                                 mult, d_floor, iters, trim)
+
+    def run_plane_rtrimmed_dev(self, planes, T_dev, stats, rmax, frac, mult=1.0, d_floor=0.0, iters=4, trim=None):
+        """run_plane_trimmed_dev with trim_keys_plane in place of trim_keys: every iteration trims each
+        segment by its pairs' plane residual at its pose.  Six launches per iteration; returns trim
+        as there."""
+        return self._run_trimmed(self.ctx.lib.pcp_icp_batch_run_plane_rtrimmed_dev, planes, T_dev, stats, rmax, frac,
+                                 mult, d_floor, iters, trim)
 
     def close(self):
         if getattr(self, "h", None):

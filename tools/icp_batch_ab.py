@@ -19,7 +19,15 @@ the segment sums; solve_plane_dev; one iteration of run_plane_dev).  With --no-l
 side runs.  With --trace two batched create + run rounds and nothing else, for a kernel trace.  The
 8 x 160000 shape of DESIGN.md 5.1d is --segs 8 --per 160000 --window 50.
 
+With --trimmed the windows overlap the map only in part: the last quarter of every window's queries
+is replaced by clutter 0.15 .. 0.45 m above the ground of its own window (trim_ref.cluttered_queries
+of the tests), and both legs run the loop that trims by the plane residual (pcp.h I3b / I5b) at
+rtrim_ref.SCENE_RTRIM: (a) ICPBatch create + run_plane_rtrimmed_dev, (b) segs x (ICP create +
+run_plane_rtrimmed_dev).  The entries then also time the batch's trim alone and the untrimmed
+run_plane_dev on the same batch, and every window's error is listed.
+
     python tools/icp_batch_ab.py [--segs 64 --per 20000 --window 20] [--reps 5] [--no-loop] [--trace]
+                                 [--trimmed]
 """
 import argparse
 import json
@@ -31,7 +39,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from pointcloudprocess_amd import ops, synth  # noqa: E402
+import rtrim_ref  # noqa: E402
+import trim_ref  # noqa: E402
 
 RMAX = 0.5
 ITERS = 4
@@ -51,8 +62,9 @@ def summary(ms):
     return {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
 
 
-def make_segments(n_scene, segs, per, window, device, seed=4102):
-    """(q (segs * per, 3) fp32 on the device, offsets, T_true (segs, 4, 4))."""
+def make_segments(n_scene, segs, per, window, device, seed=4102, clutter=0.0):
+    """(q (segs * per, 3) fp32 on the device, offsets, T_true (segs, 4, 4)).  clutter: the share of
+    every window's queries replaced by points that have no counterpart in the target."""
     scene = synth.street_scene(n_scene, seed, device=device)
     rng = np.random.default_rng(seed)
     g = torch.Generator(device="cpu")
@@ -72,7 +84,13 @@ def make_segments(n_scene, segs, per, window, device, seed=4102):
         T = synth.rigid(ang[0], ang[1], ang[2], t=tuple(rng.uniform(-0.08, 0.08, 3)))
         c = np.array([float(xs[s]), STREET_Y, 0.0])
         T[:3, 3] += c - T[:3, :3] @ c
-        out.append(synth.apply_inverse(pts[pick], T))
+        seg = synth.apply_inverse(pts[pick], T)
+        if clutter > 0:
+            Tc = T.copy()  # cluttered_queries scatters about the origin: move the window's centre there
+            Tc[:3, 3] -= c
+            seg = torch.from_numpy(trim_ref.cluttered_queries(seg.cpu().numpy(), Tc, share=clutter, half=half,
+                                                              seed=seed + s)).to(device)
+        out.append(seg)
         Ts.append(T)
     off = np.arange(segs + 1, dtype=np.int64) * per
     return torch.cat(out).contiguous(), off, np.stack(Ts)
@@ -88,6 +106,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--trimmed", action="store_true", help="25 %% clutter per window, residual-trimmed loops")
     args = ap.parse_args()
     ctx = ops.Context(0)
     dev = ctx.device
@@ -97,31 +116,48 @@ def main():
     ix64.close()
     index = ops.GridIndex(ctx, tgt, cell_size=0.25)
     planes = ops.IcpPlanes(ctx, tgt, rows)
-    q, off, T_true = make_segments(args.scene, args.segs, args.per, args.window, dev)
+    q, off, T_true = make_segments(args.scene, args.segs, args.per, args.window, dev,
+                                   clutter=0.25 if args.trimmed else 0.0)
     B = args.segs
     segq = [q[int(off[s]):int(off[s + 1])] for s in range(B)]
     eye = torch.eye(4, dtype=torch.float64, device=dev).reshape(1, 16).repeat(B, 1).contiguous()
     T_b, st_b = eye.clone(), torch.zeros((B, 4), dtype=torch.float64, device=dev)
     T_l, st_l = eye.clone(), torch.zeros((B, 4), dtype=torch.float64, device=dev)
 
+    tr_b = torch.zeros((B, 4), dtype=torch.int64, device=dev)
+    tr_l = torch.zeros((B, 4), dtype=torch.int64, device=dev)
+    RT = rtrim_ref.SCENE_RTRIM
+
     def reset():
         T_b.copy_(eye); st_b.zero_(); T_l.copy_(eye); st_l.zero_()
 
+    def run_batch(b, iters=ITERS):
+        if args.trimmed:
+            b.run_plane_rtrimmed_dev(planes, T_b, st_b, RMAX, *RT, iters=iters, trim=tr_b)
+        else:
+            b.run_plane_dev(planes, T_b, st_b, RMAX, iters)
+
+    def run_single(h, s):
+        if args.trimmed:
+            h.run_plane_rtrimmed_dev(planes, segq[s], T_l[s], st_l[s], RMAX, *RT, iters=ITERS, trim=tr_l[s])
+        else:
+            h.run_plane_dev(planes, segq[s], T_l[s], st_l[s], RMAX, ITERS)
+
     def batch_total():
         b = ops.ICPBatch(index, q, off)
-        b.run_plane_dev(planes, T_b, st_b, RMAX, ITERS)
+        run_batch(b)
         return [b]
 
     def loop_total():
         hs = []
         for s in range(B):
             h = ops.ICP(index, segq[s])
-            h.run_plane_dev(planes, segq[s], T_l[s], st_l[s], RMAX, ITERS)
+            run_single(h, s)
             hs.append(h)
         return hs
 
     res = {"segs": B, "per": args.per, "window_m": args.window, "target": args.target, "iters": ITERS, "rmax": RMAX,
-           "reps": args.reps, "build": ctx.lib.pcp_build_id().decode()}
+           "reps": args.reps, "trimmed": list(RT) if args.trimmed else None, "build": ctx.lib.pcp_build_id().decode()}
     if args.trace:
         for _ in range(2):
             reset()
@@ -147,7 +183,7 @@ def main():
         reset()
         b = ops.ICPBatch(index, q, off)
         ctx.sync()
-        t, _ = timed(lambda: b.run_plane_dev(planes, T_b, st_b, RMAX, ITERS))
+        t, _ = timed(lambda: run_batch(b))
         b.close()
         if r:
             ms["batch_run"].append(t)
@@ -157,7 +193,7 @@ def main():
 
             def loop_run():
                 for s in range(B):
-                    hs[s].run_plane_dev(planes, segq[s], T_l[s], st_l[s], RMAX, ITERS)
+                    run_single(hs[s], s)
             t, _ = timed(loop_run)
             for h in hs:
                 h.close()
@@ -171,7 +207,11 @@ def main():
     # pose error per segment: where the window's centre lands, and the rotation angle left
     xs = np.linspace(-100.0 + args.window / 2 + 2.0, 100.0 - args.window / 2 - 2.0, B)
     cen = [np.array([x, STREET_Y, 0.0, 1.0]) for x in xs]
-    res["max_centre_err_m"] = float(max(np.linalg.norm((Tb[s] - T_true[s]) @ cen[s]) for s in range(B)))
+    cerr = [float(np.linalg.norm((Tb[s] - T_true[s]) @ cen[s])) for s in range(B)]
+    res["max_centre_err_m"] = max(cerr)
+    if args.trimmed:
+        res["centre_err_mm_per_window"] = [round(1e3 * e, 3) for e in cerr]
+        res["kept_per_window_last_iteration"] = tr_b[:, 1].cpu().tolist()
     dR = [Tb[s][:3, :3] @ T_true[s][:3, :3].T for s in range(B)]
     res["max_angle_err_deg"] = float(max(np.degrees(np.arccos(np.clip((np.trace(r) - 1) / 2, -1, 1))) for r in dR))
     if not args.no_loop:
@@ -186,7 +226,12 @@ def main():
     entry = {"keys_dev": lambda: b.keys_dev(eye, RMAX, out=keys),
              "accumulate_plane": lambda: b.accumulate_plane(eye, keys, planes, acc=acc),
              "solve_plane_dev": lambda: b.solve_plane_dev(acc, T_b, st_b),
-             "run_1_iteration": lambda: b.run_plane_dev(planes, T_b, st_b, RMAX, 1)}
+             "run_1_iteration": lambda: run_batch(b, 1)}
+    if args.trimmed:
+        tkeys = torch.empty_like(keys)
+        entry["trim_keys_plane"] = lambda: b.trim_keys_plane(eye, keys, planes, *RT, out=tkeys)
+        entry["run_rtrimmed"] = lambda: run_batch(b)
+        entry["run_untrimmed_same_batch"] = lambda: b.run_plane_dev(planes, T_b, st_b, RMAX, ITERS)
     ems = {k: [] for k in entry}
     for r in range(args.reps + 1):
         for k, fn in entry.items():
