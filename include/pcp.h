@@ -353,7 +353,14 @@ int pcp_icp_accumulate_owned(pcp_ctx* ctx, const double* T_dev, const float* q_d
  * context stream). */
 int pcp_slab_guard(pcp_ctx* ctx, const double* T_dev, const double box_host[6], double lo,
                    double hi, int* flag_dev);
-/* Host Kabsch/Umeyama solve of the increment dT from 24 accumulators (host memory). */
+/* Host Kabsch/Umeyama solve of the increment dT from 24 accumulators (host memory): with qm, pm
+ * the means and S = acc[7..15] - n qm pm^T = U diag(s) V^T (one-sided Jacobi), R = V diag(1, 1,
+ * det(V U^T)) U^T, sc = (s0 + s1 + det s2) / sum |q - qm|^2 with do_scale (else 1), t = pm - sc R qm;
+ * dT = [sc R, t].  Planar and collinear pairs complete their basis to a proper rotation.
+ * Rank 0 -- s0 <= 64 eps max(|acc[7..15]|, n |qm| |pm|), i.e. S is no more than the rounding of
+ * the sums it is formed from (every pair at one target point, or every query at one point) --
+ * prefers no rotation: dT = [I, pm - qm] with scale 1, PCP_OK.
+ * PCP_ERR_ICP (dT untouched) when acc[0] < 3 or any of acc[0..22] is a NaN or an infinity. */
 int pcp_icp_solve(const double acc_host[24], int do_scale, double dT_host[16]);
 /* Full loop: T_inout (row-major), `iters` iterations (stops early when the increment's
  * rotation and translation fall below eps, eps <= 0 = never).  *err = RMS distance of
@@ -366,9 +373,12 @@ int pcp_icp_last_kernel_ms(const pcp_icp* icp, double* ms, int* launches);
 /* Device-resident iteration (no host round trip per iteration; multi-GPU callers insert
  * their all-reduce of acc_dev between the two calls on the same stream).  T_dev: 16 doubles
  * row-major in device memory.  pcp_icp_step_dev = pcp_icp_step for the pose in T_dev.
- * pcp_icp_solve_dev: Kabsch/Umeyama solve of acc_dev on the device and T_dev <- dT * T_dev;
- * stats_dev (4 doubles, zeroed by the caller) = [status (0 ok, -1 failed: T frozen), rms of
- * the last solved step, running sum of fallback queries, iterations solved].
+ * pcp_icp_solve_dev: pcp_icp_solve's solve of acc_dev in one device thread (the same code, rank 0
+ * and refusals included) and T_dev <- dT * T_dev; stats_dev (4 doubles, zeroed by the caller) =
+ * [status (0 ok, -1 failed), sqrt(acc[22] / acc[0]) = rms of the last solved step, running sum of
+ * acc[23] (fallback queries), iterations solved].  A refused solve (fewer than 3 pairs, a
+ * non-finite accumulator) latches status -1 and leaves T_dev, the rms and the iteration count as
+ * they were; every later call on those stats returns at once, so T_dev stays frozen.
  * pcp_icp_run_dev = iters x (step_dev + solve_dev), no convergence test (get_rot_icp with a
  * fixed iteration count; point_cloud_helper.cpp:75-166). */
 int pcp_icp_step_dev(pcp_ctx* ctx, pcp_icp* icp, const double* T_dev, float rmax, double* acc_dev);

@@ -1898,9 +1898,16 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     return PCP_OK;
 }
 
+// S = acc[7..15] - n qm pm^T cancels down from `scale` = max(|acc[7..15]|, n |qm| |pm|): each entry
+// carries a few eps * scale of rounding, so a largest singular value within kRank0 eps * scale is
+// noise, not a direction (every pair at one target point, or every query at one point).
+constexpr double kRank0 = 64.0, kEps = 2.220446049250313e-16;
+
 __host__ __device__ int icp_solve(const double acc[24], int do_scale, double dT[16]) {
     const double n = acc[0];
     if (!(n >= 3.0)) return PCP_ERR_ICP;
+    for (int k = 0; k < 23; k++)  // a NaN or an infinity among the sums (false for a NaN)
+        if (!(fabs(acc[k]) <= 1.7976931348623157e308)) return PCP_ERR_ICP;
     double qm[3], pm[3], S[9];
     for (int k = 0; k < 3; k++) { qm[k] = acc[1 + k] / n; pm[k] = acc[4 + k] / n; }
     // S = sum (q - qm)(p - pm)^T ; optimal R maximises trace(R S): S = U s V^T, R = V D U^T
@@ -1908,12 +1915,17 @@ __host__ __device__ int icp_solve(const double acc[24], int do_scale, double dT[
         for (int b = 0; b < 3; b++) S[3 * a + b] = acc[7 + 3 * a + b] - n * qm[a] * pm[b];
     double U[9], s[3], V[9];
     svd3(S, U, s, V);
+    double scale = n * sqrt((qm[0] * qm[0] + qm[1] * qm[1] + qm[2] * qm[2]) *
+                            (pm[0] * pm[0] + pm[1] * pm[1] + pm[2] * pm[2]));
+    for (int k = 7; k < 16; k++) scale = fmax(scale, fabs(acc[k]));
+    // rank 0: no rotation is preferred, so none is made (the pairs' centroids still align)
+    const bool rank0 = !(s[0] > kRank0 * kEps * scale);
     double R[9];
     for (int a = 0; a < 3; a++)
         for (int b = 0; b < 3; b++) {
             double v = 0;
             for (int k = 0; k < 3; k++) v += V[3 * a + k] * U[3 * b + k];
-            R[3 * a + b] = v;
+            R[3 * a + b] = rank0 ? (a == b ? 1.0 : 0.0) : v;
         }
     double d = det3(R) < 0 ? -1.0 : 1.0;
     if (d < 0) {  // flip the axis of the smallest singular value
@@ -1921,7 +1933,7 @@ __host__ __device__ int icp_solve(const double acc[24], int do_scale, double dT[
             for (int b = 0; b < 3; b++) R[3 * a + b] -= 2.0 * V[3 * a + 2] * U[3 * b + 2];
     }
     double sc = 1.0;
-    if (do_scale) {
+    if (do_scale && !rank0) {
         const double var = (acc[16] + acc[19] + acc[21]) - n * (qm[0] * qm[0] + qm[1] * qm[1] + qm[2] * qm[2]);
         if (var > 0) sc = (s[0] + s[1] + d * s[2]) / var;
     }
