@@ -298,10 +298,27 @@ int pcp_icp_create_with_target(pcp_ctx* ctx, const float* target_dev, size_t tar
 /* not an ablation: switch the look-ahead search centre off.  By default a query that has to be
  * searched again is searched around a point ahead of it on its path, c = T_c q with
  * T_c = T_t + beta (T_t - T_{t-1}), so that its cache certifies more of the coming launches
- * (DESIGN.md 5.1); beta comes from the ratio of the last two steps and is 0 at the first two
- * launches and whenever the step did not shrink.  With this flag beta = 0 on every launch and
- * the search kernels are the plain ones.  Results are identical either way. */
+ * (DESIGN.md 5.1); beta comes from the ratio of the last two steps and is 0 at the second launch
+ * and whenever the step did not shrink; the first launch's comes from the pilot step (below).
+ * With this flag beta = 0 on every launch and the search kernels are the plain ones.  Results
+ * are identical either way. */
 #define PCP_ICP_OPT_NO_LOOKAHEAD 512
+/* The pilot step.  Before the first launch of a handle over a dense grid, one Kabsch step over a
+ * spatially uniform sample of the queries (every S-th 64-query chunk of the sorted queries,
+ * S = max(1, chunks / 8192)) predicts the second pose T_1, and the first launch searches around
+ * c = T_c q with T_c = T_0 + beta_0 (T_1 - T_0), beta_0 = min(1.5, 45 mm / largest displacement of
+ * the predicted step): its caches then outlive the two largest steps of the registration.  When
+ * the pilot finds fewer than 3 pairs or non-finite sums, or predicts no motion, beta_0 = 0 and the
+ * first launch is the plain one.  On by default when the look-ahead is on and the handle has at
+ * least 2^25 queries (below that the pilot costs more than 5 % of the first launch).  Only
+ * pcp_icp_step / _step_dev / _run / _run_dev launches take it: the point-to-plane, trimmed and
+ * batched loops minimise something else and run without it (unmeasured there).
+ *   PCP_ICP_OPT_NO_PILOT: never run the pilot (the first launch as before, unless
+ *     pcp_icp_predict_first supplied a pose).
+ *   PCP_ICP_OPT_PILOT_ALWAYS: run it below the size threshold too (tests).
+ * Results are identical either way. */
+#define PCP_ICP_OPT_NO_PILOT 1024
+#define PCP_ICP_OPT_PILOT_ALWAYS 2048
 int pcp_icp_set_options(pcp_icp* icp, int oct_lanes_first, int oct_lanes_list, int ring_lanes, int ablate);
 int pcp_icp_destroy(pcp_icp* icp);
 /* One iteration at pose T (row-major 4x4 double, cast to fp32 for the kernel):
@@ -397,6 +414,17 @@ int pcp_icp_last_searched(const pcp_icp* icp, int64_t* n);
  * |c - q_t| (metres) over the corners of the target grid's box grown by rmax.  Both 0 when the
  * launch searched around q_t itself. */
 int pcp_icp_last_lookahead(const pcp_icp* icp, double* beta, double* max_offset_m);
+/* The caller's prediction of the pose of the handle's SECOND launch (row-major 4x4), from a motion
+ * prior say: it replaces the pilot step (none is run) and the first launch looks ahead towards it
+ * as described at PCP_ICP_OPT_NO_PILOT, whatever the handle's size.  Only before the first launch
+ * (PCP_ERR_ARG afterwards); ignored on a sparse grid and with PCP_ICP_OPT_NO_LOOKAHEAD.  A wrong
+ * prediction costs later searches, never exactness; one equal to the first pose or not finite gives
+ * beta_0 = 0. */
+int pcp_icp_predict_first(pcp_icp* icp, const double T1[16]);
+/* What the pilot step of the handle's first launch did (waits for it): the chunk stride S, the
+ * number of 64-query chunks it sampled (chunks 0, S, 2S, ...) and the pairs it accumulated.
+ * stride = chunks = 0 and pairs = -1 when no pilot ran. */
+int pcp_icp_pilot_info(const pcp_icp* icp, int64_t* stride, int64_t* chunks, int64_t* pairs);
 
 /* PointCloudHelper::get_rot_icp (point_cloud_helper.cpp:75-166) on AoS48 clouds:
  * joint centroid (sequential fold over src ++ temp; non-finite points skipped unless both

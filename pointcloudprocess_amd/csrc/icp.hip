@@ -83,6 +83,11 @@ struct pcp_icp {
     bool graph_off = false;          // capture failed: plain launches
     bool graph = false;              // PCP_ICP_OPT_GRAPH
     bool no_look = false;            // PCP_ICP_OPT_NO_LOOKAHEAD: beta = 0, the plain search kernels
+    bool no_pilot = false;           // PCP_ICP_OPT_NO_PILOT: no pilot step before the first launch
+    bool pilot_always = false;       // PCP_ICP_OPT_PILOT_ALWAYS: the pilot below kPilotMinQueries too
+    bool has_pred = false;           // pcp_icp_predict_first: pred replaces the pilot's estimate
+    double pred[16] = {};            // the caller's predicted second pose
+    double* pilot_acc = nullptr;     // 24: the pilot's reduced accumulators
 };
 
 namespace pcp {
@@ -143,6 +148,9 @@ struct IcpArgs {
     int ring_g;         // fallback pass lanes per query: 1, 2, 4, 8, or 0 = by the list's length
     const float* pose;  // device poses (current, previous: 24 floats) overriding R/t, Rp/tq, or null
     const uint32_t* launch_dev;  // device copy of `launch` (k_pose_set), so a captured launch graph replays
+    int when_beta;      // first launch after a pilot: 1 = run only if the pose block's beta > 0, 2 = only
+                        // if it is 0 (the look-ahead and the plain kernel are both enqueued), 0 = always
+    int64_t pilot_stride;  // k_icp_pilot: every pilot_stride-th 64-query chunk is sampled
 };
 
 // sorted query i as {x, y, z, 0}
@@ -162,7 +170,7 @@ __device__ __forceinline__ void load_pose(IcpArgs& a) {
     }
 }
 // the look-ahead map (pose block words kPoseC ..): equal to the pose when beta = 0
-constexpr int kPoseStep = 25, kPoseBeta = 26, kPoseOff = 27, kPoseC = 28, kPoseWords = 40;
+constexpr int kPoseStep = 25, kPoseBeta = 26, kPoseOff = 27, kPoseC = 28, kPoseWords = 41;
 __device__ __forceinline__ void load_pose_c(IcpArgs& a) {
 #pragma unroll
     for (int k = 0; k < 9; k++) a.Rc[k] = a.pose[kPoseC + k];
@@ -757,6 +765,7 @@ struct OctResult {
     uint32_t c0 = ~0u, c1 = ~0u, c2 = ~0u;  // the cache: positions of the 3 kept points
     float dnext = INFINITY;    // lower bound on the d2 of every scanned point not kept
     bool uniq = false;         // look-ahead scans: d0 / win are this launch's exact winner
+    float d1t = 0.f;           // look-ahead scans: lower bound on the d2 AT q_t of every scanned point but win
 };
 
 __device__ __forceinline__ void take_exact(OctResult& o, const float4 p, uint32_t pos, float qx, float qy, float qz,
@@ -915,6 +924,7 @@ __device__ __forceinline__ OctResult octant_packed_la(const IcpArgs& a, const ui
     const bool any = m.u0 != kKeyMax;
     o.uniq = any && (m.u1 & ~0xffu) > (m.u0 & ~0xffu);
     o.d0 = any ? __uint_as_float(m.u0 & ~0xffu) : INFINITY;
+    o.d1t = __uint_as_float(m.u1 & ~0xffu);  // every other scanned point's key is >= u1 (FLT_MAX: none)
     if (any) {
         const uint32_t w = cat_addr_l(m.u0 & 0xffu, c1, c2, c3, L, o0, o1, o2, o3, a.ntp);
         if (w != o.c0 && w != o.c1 && w != o.c2) {  // (then 4 or more were scanned: t2 is a real key)
@@ -993,17 +1003,22 @@ __device__ __noinline__ OctResult octant_exact(const IcpArgs& a, uint32_t rs0, u
 // lanes no longer share candidate lines.
 constexpr int kOctW = kIcpBlock / 64;
 //
-// LOOK (the search lists of a handle with the look-ahead on): the block, its rows, the cache and D
-// are taken around the centre c = T_c q (k_pose_set), which lies ahead on the query's path, so the
-// cached ball outlives more of the coming steps.  The certificate of the verify pass is geometry
-// about c alone, whatever c is.  This launch's own result is still the exact winner at q_t = T_t q:
-// the nearest scanned point to q_t, certified by q_t's distance to the faces of the block that was
-// scanned (a block around c may hold q_t off-centre, or not at all: then the fallback decides).
-template <int G, bool LOOK>
+// LOOK (the search lists of a handle with the look-ahead on, and its first launch after a pilot
+// step): the cache and D are taken around the centre c = T_c q (k_pose_set, k_pilot_map), which
+// lies ahead on the query's path, so the cached ball outlives more of the coming steps.  The
+// certificate of the verify pass is geometry about c alone, whatever c is.  The block scanned is
+// the one around q_t = T_t q, as in the plain form: this launch's own result, the nearest scanned
+// point to q_t, is certified by q_t's distance to its faces (>= 1/2 cell) exactly as there, so the
+// look-ahead sends no query to the fallback that the plain form would settle; D is cut by c's
+// distance to those same faces (a c outside the block gets D = 0: nothing is settled from it).
+// PILOT (k_icp_pilot): the plain scan over every pilot_stride-th chunk, accumulating the octant's
+// own winners within rmax; it writes no cache record and no list.
+template <int G, bool LOOK, bool PILOT = false>
 __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list, int64_t n,
                                            double (*s_acc)[kAcc]) {
     constexpr int kW = kOctW;
     constexpr int QPC = 64 / G;  // queries per chunk
+    static_assert(!PILOT || (G == 1 && !LOOK), "the pilot is the plain one-lane scan");
     const GridDesc& g = a.g;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int slot = lane / G;
@@ -1012,20 +1027,25 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
     const int64_t gw = (int64_t)blockIdx.x * kW + wid;  // global wave id = fallback segment
     uint32_t fbn = 0;  // wave-uniform count of this wave's fallback entries
     const int64_t nwaves = (int64_t)gridDim.x * kW;
+    // entry j of the work: the list's, the j-th query, or (PILOT) lane j % 64 of sampled chunk j / 64
+    auto query_of = [&](int64_t j) -> int64_t {
+        if constexpr (PILOT) return (j >> 6) * a.pilot_stride * 64 + (j & 63);
+        return list ? (int64_t)list[j] : j;
+    };
     int64_t in_ = 0;
     float4 qn = make_float4(0.f, 0.f, 0.f, 0.f);
     if (gw * QPC + slot < n) {
-        in_ = list ? (int64_t)list[gw * QPC + slot] : gw * QPC + slot;
-        qn = ldq(a, in_);
+        in_ = query_of(gw * QPC + slot);
+        if (!PILOT || in_ < a.nq) qn = ldq(a, in_);
     }
     for (int64_t c = gw; c * QPC < n; c += nwaves) {  // grid-stride (an XCD split measured slower here)
         const int64_t j = c * QPC + slot;
-        const bool valid = j < n;
         const int64_t i = in_;
+        const bool valid = j < n && (!PILOT || i < a.nq);  // (the last sampled chunk may be partial)
         const float4 qraw = qn;
         if (j + QPC * nwaves < n) {  // prefetch the next chunk's query
-            in_ = list ? (int64_t)list[j + QPC * nwaves] : j + QPC * nwaves;
-            qn = ldq(a, in_);
+            in_ = query_of(j + QPC * nwaves);
+            if (!PILOT || in_ < a.nq) qn = ldq(a, in_);
         }
         float qx = 0.f, qy = 0.f, qz = 0.f, fx = 0.f, fy = 0.f, fz = 0.f, dout = 0.f;
         float cx = 0.f, cy = 0.f, cz = 0.f, delta = 0.f;  // LOOK: the centre, |q_t - c| rounded up
@@ -1038,10 +1058,9 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
                 const float ex = qx - cx, ey = qy - cy, ez = qz - cz;
                 const float e2 = __fmaf_rn(ez, ez, __fmaf_rn(ey, ey, ex * ex));
                 delta = e2 > 0.f ? sqrtf(e2) * 1.00001f + 1e-7f : 0.f;
-            } else {
-                cx = qx, cy = qy, cz = qz;
             }
-            fx = cell_f<float>(g, cx, 0), fy = cell_f<float>(g, cy, 1), fz = cell_f<float>(g, cz, 2);
+            // the block is placed from q_t in both forms: q_t is never off-centre in it
+            fx = cell_f<float>(g, qx, 0), fy = cell_f<float>(g, qy, 1), fz = cell_f<float>(g, qz, 2);
             bx = (int)floorf(fx - a.rho), by = (int)floorf(fy - a.rho), bz = (int)floorf(fz - a.rho);
             // a query farther than rmax from the grid's box (a target-sharded rank: the queries
             // of the other shards) is settled "no correspondence" without a scan, with D = that
@@ -1050,9 +1069,7 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
             const float oy = fmaxf(fmaxf(-fy, fy - (float)g.n[1]), 0.f);
             const float oz = fmaxf(fmaxf(-fz, fz - (float)g.n[2]), 0.f);
             dout = fmaxf(sqrtf(__fmaf_rn(oz, oz, __fmaf_rn(oy, oy, ox * ox))) - a.mc, 0.f) * g.hf;
-            // (LOOK: dout is c's distance to the box; q_t is at least dout - delta from it)
-            const float dq = LOOK ? fmaxf(dout - delta, 0.f) : dout;
-            outside = dq * dq > a.r2 * 1.0001f;
+            outside = dout * dout > a.r2 * 1.0001f;
         }
         const bool scanq = !outside;
         uint32_t rs[4], rn[4];
@@ -1082,51 +1099,66 @@ __device__ __forceinline__ void octant_run(const IcpArgs& a, const int32_t* list
                                         fminf(fy - (float)by, (float)(by + 2) - fy)),
                                   fminf(fz - (float)bz, (float)(bz + 2) - fz)) - a.mc;
             const float rr = m * g.hf;
+            const float cert2 = fmaxf(a.cert2, rr * rr * (1.f - 2e-5f));
+            float mD = m;  // the cache's radius: the centre's distance to the same faces
             if constexpr (LOOK) {
-                // q_t's own distance to the faces of the block scanned (around c): every target
-                // nearer to q_t than that was scanned.  Not positive: q_t is outside the block.
-                const float tx = cell_f<float>(g, qx, 0), ty = cell_f<float>(g, qy, 1), tz = cell_f<float>(g, qz, 2);
-                const float mt = fminf(fminf(fminf(tx - (float)bx, (float)(bx + 2) - tx),
-                                             fminf(ty - (float)by, (float)(by + 2) - ty)),
-                                       fminf(tz - (float)bz, (float)(bz + 2) - tz)) - a.mc;
-                const float rt = mt * g.hf;
-                const float cert2 = mt > 0.f ? rt * rt * (1.f - 2e-5f) : -1.f;
+                // c's own distance to the faces of the block scanned (around q_t): every target
+                // nearer to c than that was scanned.  Not positive: c is outside the block, D = 0
+                // and the record never settles anything.
+                const float ux = cell_f<float>(g, cx, 0), uy = cell_f<float>(g, cy, 1), uz = cell_f<float>(g, cz, 2);
+                mD = fminf(fminf(fminf(ux - (float)bx, (float)(bx + 2) - ux),
+                                 fminf(uy - (float)by, (float)(by + 2) - uy)),
+                           fminf(uz - (float)bz, (float)(bz + 2) - uz)) - a.mc;
                 // o.d0 is exact with o.uniq, else a lower bound on every scanned point's d2
                 found = o.uniq && o.d0 <= a.r2;
                 settled = (found ? o.d0 <= cert2 : (o.d0 > a.r2 && a.r2 <= cert2)) || outside ||
                           (a.dbg & kDbgNoFallback);
             } else {
-                const float cert2 = fmaxf(a.cert2, rr * rr * (1.f - 2e-5f));
                 found = o.d0 <= a.r2;
                 settled = (found ? (o.d0 < o.dnext && o.d0 <= cert2) : a.r2 <= cert2) || outside ||
                           (a.dbg & kDbgNoFallback);
             }
-            // the cache: the 3 nearest; settled: D bounds every uncached point for the verify
-            // pass.  Unsettled: the fallback pass (which overwrites the cache) gets the
-            // octant's first uncached d2 instead.
-            // (unsettled: the message is the octant's first uncached distance, rounded down)
-            const float D = outside ? dout * 0.9999f
-                                    : (settled ? fminf(sqrtf(o.dnext), (m > 0.f ? m : 0.f) * g.hf) * 0.9999f
-                                               // (LOOK: dnext is measured from c; the fallback's skip
-                                               // proof needs the bound at q_t)
-                                               : fmaxf(sqrtf(o.dnext) - delta, 0.f) * 0.99999f);
-            if (lead) cache_store(a, i, o.c0, o.c1, o.c2, D, a.launch);
+            if constexpr (PILOT) {
+                // the octant's nearest within rmax, certified or not: a prediction needs no exactness,
+                // and leaving out the far pairs (the ones that move the pose most) measured a first
+                // step 20 % short on the C4 registration
+                settled = found;
+            } else {
+                // the cache: the 3 nearest; settled: D bounds every uncached point for the verify
+                // pass.  Unsettled: the fallback pass (which overwrites the cache) gets the
+                // octant's first uncached d2 instead.
+                // (unsettled: the message is the octant's first uncached distance, rounded down)
+                // (LOOK: dout and dnext's fallback message are bounds at q_t, D is one at c)
+                const float D = outside ? fmaxf(dout - delta, 0.f) * 0.9999f
+                                        : (settled ? fminf(sqrtf(o.dnext), (mD > 0.f ? mD : 0.f) * g.hf) * 0.9999f
+                                                   // (LOOK: dnext is measured from c and the fallback's skip
+                                                   // proof needs the bound at q_t: dnext less |q_t - c|, or
+                                                   // the second smallest d2 at q_t -- the winner is cached,
+                                                   // so every uncached point is at least that far)
+                                                   : fmaxf(sqrtf(o.dnext) - delta, LOOK ? sqrtf(o.d1t) : 0.f) *
+                                                         0.99999f);
+                if (lead) cache_store(a, i, o.c0, o.c1, o.c2, D, a.launch);
+            }
         }
-        // ---- fallback list (ballot + mbcnt, no atomics) and accumulators
-        const bool fb = valid && lead && !settled;
-        const uint64_t fbm = __ballot(fb);
-        if (fb) {
-            const uint32_t pos = fbn + __builtin_amdgcn_mbcnt_hi((uint32_t)(fbm >> 32),
-                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)fbm, 0u));
-            a.fb[gw * a.fb_seg + pos] = (int32_t)i;
+        if constexpr (!PILOT) {
+            // ---- fallback list (ballot + mbcnt, no atomics) and accumulators
+            const bool fb = valid && lead && !settled;
+            const uint64_t fbm = __ballot(fb);
+            if (fb) {
+                const uint32_t pos = fbn + __builtin_amdgcn_mbcnt_hi((uint32_t)(fbm >> 32),
+                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)fbm, 0u));
+                a.fb[gw * a.fb_seg + pos] = (int32_t)i;
+            }
+            fbn += (uint32_t)__popcll(fbm);
         }
-        fbn += (uint32_t)__popcll(fbm);
         const bool acc_ok = valid && lead && settled && found && !(a.dbg & kDbgNoAccum);
         const Best w{o.d0, 0, o.win, o.wx, o.wy, o.wz};
         chunk_accumulate(acc_ok, qx, qy, qz, w, s_acc[wid], lane);
     }
-    if (lane == 0) {  // every wave of the grid writes its count: no zeroing pass needed
-        a.fb_count[gw] = fbn;
+    if constexpr (!PILOT) {
+        if (lane == 0) {  // every wave of the grid writes its count: no zeroing pass needed
+            a.fb_count[gw] = fbn;
+        }
     }
 }
 
@@ -1146,6 +1178,8 @@ __device__ __forceinline__ int octant_lanes(int64_t n, int64_t nq) {
 template <int MINW, bool LOOK>
 __global__ void __launch_bounds__(kIcpBlock, MINW) k_icp_octant(IcpArgs a, const int32_t* list,
                                                                  const uint32_t* list_n) {
+    // the first launch after a pilot step: the form that beta_0 (k_pilot_map) did not choose exits
+    if (a.when_beta && (a.pose[kPoseBeta] > 0.f) != (a.when_beta == 1)) return;
     load_pose(a);
     if constexpr (LOOK) load_pose_c(a);
     __shared__ double s_acc[kOctW][kAcc];
@@ -1170,6 +1204,20 @@ __global__ void __launch_bounds__(kIcpBlock, MINW) k_icp_octant(IcpArgs a, const
             a.fb_count[sg] = 0u;
         }
     }
+}
+
+// Pilot step (before a handle's first launch, dense grid): the plain octant scan under the first
+// launch's pose over every a.pilot_stride-th 64-query chunk of the sorted queries -- a spatially
+// uniform sample, since the queries are sorted by cell -- accumulating the nearest scanned target of
+// every query that has one within rmax (the exact winner for most).  One Kabsch step over these sums (k_pilot_map) predicts the second pose.  `nsamp`
+// sampled chunks, one per wave, grid-stride; workgroup b writes partial row b.
+__global__ void __launch_bounds__(kIcpBlock, PCP_OCT_WAVES) k_icp_pilot(IcpArgs a, int64_t nsamp) {
+    load_pose(a);
+    __shared__ double s_acc[kOctW][kAcc];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane < kAcc) s_acc[wid][lane] = 0.0;
+    octant_run<1, false, true>(a, nullptr, nsamp * 64, s_acc);
+    write_wave_partials(s_acc, a.partials + (int64_t)blockIdx.x * kAcc);
 }
 
 // Fallback / general pass: exact box search (dense or sparse grid), starting from the
@@ -1217,7 +1265,7 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
             // the search pass left this launch's octant message: the 4th smallest distance of
             // its octant (rounded down).  Above the cached best, every octant point tied with
             // that best is cached, so the cached best IS the octant's (d2, index) winner and its
-            // cells need no rescan.  (A look-ahead search scanned the block around its centre
+            // cells need no rescan.  (A look-ahead search ranked what it cached around its centre
             // c = T_c q, and its message is already weakened by |q_t - c| to a bound at q_t.)
             const bool skip_oct = !a.ring_all && cd.slot == (a.launch & a.hist_mask) && cd.D * cd.D > cbst.bd;
             bool done = false;
@@ -1230,12 +1278,10 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
                 const float fx = cell_f<float>(g, qx, 0), fy = cell_f<float>(g, qy, 1), fz = cell_f<float>(g, qz, 2);
                 const int cx = (int)floorf(fx), cy = (int)floorf(fy), cz = (int)floorf(fz);
                 const float lx = fx - (float)cx, ly = fy - (float)cy, lz = fz - (float)cz;
-                // the block the octant pass scanned: chosen from c (= q_t when beta = 0)
-                float ccx, ccy, ccz;
-                xform_c(a, qraw, ccx, ccy, ccz);
-                const int bxo = (int)floorf(cell_f<float>(g, ccx, 0) - a.rho),
-                          byo = (int)floorf(cell_f<float>(g, ccy, 1) - a.rho),
-                          bzo = (int)floorf(cell_f<float>(g, ccz, 2) - a.rho);
+                // the block the octant pass scanned: placed from q_t in every form (octant_run),
+                // by the same expression
+                const int bxo = (int)floorf(fx - a.rho), byo = (int)floorf(fy - a.rho),
+                          bzo = (int)floorf(fz - a.rho);
                 const float inv_h2 = g.inv_hf * g.inv_hf;
                 const float gxl = sq_gap(lx, a.mc), gxr = sq_gap(1.f - lx, a.mc);
                 for (int dz = -1; dz <= 1; dz++) {
@@ -1287,7 +1333,6 @@ __device__ __forceinline__ void ring_run(IcpArgs& a, double (*s_acc)[kAcc], cons
 __global__ void __launch_bounds__(kIcpBlock, PCP_RING_WAVES) k_icp_ring(IcpArgs a, double* partials,
                                                                         const int32_t* list, const uint32_t* list_n) {
     load_pose(a);
-    load_pose_c(a);
     constexpr int kW = kIcpBlock / 64;
     __shared__ double s_acc[kW][kAcc];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -1628,9 +1673,10 @@ __host__ __device__ double det3(const double M[9]) {
 // rebuilds c) and beside the pose (where the search kernels read it).  Exactness never depends on
 // it: the certificate holds for any centre; beta only decides how many later searches there are.
 // The step's size is its largest displacement over the corners of `box`, the target grid's box
-// grown by rmax (it holds every query that can have a correspondence); beta = 0 at the first two
-// launches (no ratio yet), when the step did not shrink (a pose jump included), and it is cut so
-// that no corner's offset exceeds cap.
+// grown by rmax (it holds every query that can have a correspondence); beta = 0 at the second
+// launch (no ratio yet), when the step did not shrink (a pose jump included), and it is cut so
+// that no corner's offset exceeds cap.  The first launch has no step behind it at all: its beta
+// comes from a predicted second pose (the pilot step or the caller's, k_pilot_map), else it is 0.
 struct LookAhead {
     float lo[3], hi[3];  // the box
     float alpha, cap;    // fraction of the predicted remaining path; largest offset (m)
@@ -1640,17 +1686,29 @@ struct LookAhead {
 #define PCP_LOOK_ALPHA 0.5f
 #endif
 constexpr float kLookAlpha = PCP_LOOK_ALPHA, kLookCap = 0.02f, kLookRmax = 0.9f;
-__global__ void k_pose_set(const double* T, Pose32 hp, LookAhead la, float* pose, float* hist, uint32_t launch) {
-    *(uint32_t*)(pose + 24) = launch;
-    for (int k = 0; k < 12; k++) pose[12 + k] = pose[k];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) pose[3 * r + c] = T ? (float)T[4 * r + c] : hp.R[3 * r + c];
-        pose[9 + r] = T ? (float)T[4 * r + 3] : hp.t[r];
-    }
-    // this step's displacement of a point y (target frame): y - T_{t-1} T_t^-1 y = M y + v
+// The first launch's look-ahead (k_pilot_map): beta_0 = min(kPilotAlpha, kPilotCap / s_1) with s_1
+// the predicted first step's size.  The first step is the largest of the registration and the
+// second is still large, so the centre goes further than one step when the cap allows
+// (tools/sim_icp_pilot.py sweeps both).
+#ifndef PCP_PILOT_ALPHA
+#define PCP_PILOT_ALPHA 1.5f
+#endif
+#ifndef PCP_PILOT_CAP
+#define PCP_PILOT_CAP 0.045f
+#endif
+constexpr float kPilotAlpha = PCP_PILOT_ALPHA, kPilotCap = PCP_PILOT_CAP;
+constexpr int64_t kPilotChunks = 8192;  // the pilot samples about this many 64-query chunks
+// the pilot runs by default from this many queries: its cost is about constant (three launches and
+// ~8K chunks, ~0.06 ms), below 5 % of a first launch that takes ~44 us per million queries
+constexpr int64_t kPilotMinQueries = (int64_t)1 << 25;
+constexpr int kPilotPairs = 40;  // pose block word: the pilot's pair count (float), -1 = no pilot ran
+
+// the size of the step from pose `prev` to pose `cur` (12 floats each: R row-major, t): the largest
+// displacement y - T_prev T_cur^-1 y = y - (M y - v) over the corners y of the box
+__device__ double step_size(const float* cur, const float* prev, const LookAhead& la) {
     double A[9], B[9], ta[3], tb[3], Ai[9], BA[9], v[3];
-    for (int k = 0; k < 9; k++) { A[k] = pose[k]; B[k] = pose[12 + k]; }
-    for (int k = 0; k < 3; k++) { ta[k] = pose[9 + k]; tb[k] = pose[21 + k]; }
+    for (int k = 0; k < 9; k++) { A[k] = cur[k]; B[k] = prev[k]; }
+    for (int k = 0; k < 3; k++) { ta[k] = cur[9 + k]; tb[k] = prev[9 + k]; }
     const double det = det3(A);
     Ai[0] = A[4] * A[8] - A[5] * A[7]; Ai[1] = A[2] * A[7] - A[1] * A[8]; Ai[2] = A[1] * A[5] - A[2] * A[4];
     Ai[3] = A[5] * A[6] - A[3] * A[8]; Ai[4] = A[0] * A[8] - A[2] * A[6]; Ai[5] = A[2] * A[3] - A[0] * A[5];
@@ -1669,9 +1727,21 @@ __global__ void k_pose_set(const double* T, Pose32 hp, LookAhead la, float* pose
         }
         s2 = fmax(s2, d2);
     }
-    const float step = launch > 0 ? (float)sqrt(s2) : 0.f, prev = pose[kPoseStep];
+    return sqrt(s2);
+}
+
+__global__ void k_pose_set(const double* T, Pose32 hp, LookAhead la, float* pose, float* hist, uint32_t launch) {
+    *(uint32_t*)(pose + 24) = launch;
+    for (int k = 0; k < 12; k++) pose[12 + k] = pose[k];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) pose[3 * r + c] = T ? (float)T[4 * r + c] : hp.R[3 * r + c];
+        pose[9 + r] = T ? (float)T[4 * r + 3] : hp.t[r];
+    }
+    // this step's displacement of a point y (target frame)
+    const float step = launch > 0 ? (float)step_size(pose, pose + 12, la) : 0.f, prev = pose[kPoseStep];
     float beta = 0.f;
-    // launch 1 has no previous step, so no ratio and no look-ahead
+    // launch 1 has no previous step, so no ratio and no look-ahead; launch 0's comes from the pilot
+    // step, if there is one (k_pilot_map overwrites the words written here)
     const float ratio = launch == 1 ? 0.f : (prev > 0.f ? step / prev : 0.f);
     if (!la.off && launch > 0 && step > 0.f && ratio > 0.f && ratio < 1.f) {  // (false for a NaN)
         const float r = fminf(ratio, kLookRmax);
@@ -1681,12 +1751,61 @@ __global__ void k_pose_set(const double* T, Pose32 hp, LookAhead la, float* pose
     pose[kPoseStep] = step;
     pose[kPoseBeta] = beta;
     pose[kPoseOff] = beta * step;
+    if (launch == 0) pose[kPilotPairs] = -1.f;
     // T_c: beta = 0 gives the pose itself, bit for bit
     for (int k = 0; k < 12; k++) pose[kPoseC + k] = __fmaf_rn(beta, pose[k] - pose[12 + k], pose[k]);
     for (int k = 0; k < 12; k++) hist[k] = pose[kPoseC + k];
 }
 
 __host__ __device__ int icp_solve(const double acc[24], int do_scale, double dT[16]);
+
+// The first launch's look-ahead map, after k_pose_set(launch 0) and before the first search.  One
+// thread.  The predicted second pose T_1 is the caller's (pred.on: pcp_icp_predict_first) or one
+// Kabsch step (no scale) over the pilot's sums, dT * T_0 with T_0 the fp32 pose of the block; then
+// beta_0 = min(kPilotAlpha, kPilotCap / s_1), s_1 the step's size as in k_pose_set, and
+// T_c = T_0 + beta_0 (T_1 - T_0) goes to the pose block and to history slot 0.  A refused solve
+// (fewer than 3 pairs, non-finite sums), a non-finite prediction or s_1 = 0 leave beta_0 = 0 and the
+// block as k_pose_set wrote it: the first launch is then the plain one.
+struct PilotPred {
+    int on;
+    double T1[16];
+};
+__global__ void k_pilot_map(const double* acc, PilotPred pred, LookAhead la, float* pose, float* hist) {
+    double T1[16];
+    if (pred.on) {
+        for (int k = 0; k < 16; k++) T1[k] = pred.T1[k];
+    } else {
+        double a[24], dT[16];
+        for (int k = 0; k < 24; k++) a[k] = acc[k];
+        pose[kPilotPairs] = (float)a[0];
+        if (icp_solve(a, 0, dT) != PCP_OK) return;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 4; j++) {
+                double v = j == 3 ? dT[4 * i + 3] : 0.0;
+                for (int k = 0; k < 3; k++) v += dT[4 * i + k] * (double)(j == 3 ? pose[9 + k] : pose[3 * k + j]);
+                T1[4 * i + j] = v;
+            }
+    }
+    float p1[12];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) p1[3 * r + c] = (float)T1[4 * r + c];
+        p1[9 + r] = (float)T1[4 * r + 3];
+    }
+    for (int k = 0; k < 12; k++)
+        if (!(fabsf(p1[k]) <= 3.4028234e38f)) return;  // (false for a NaN)
+    const float step = (float)step_size(p1, pose, la);
+    if (la.off || !(step > 0.f) || !(step <= 3.4028234e38f)) return;
+    const float beta = fminf(kPilotAlpha, kPilotCap / step);
+    float Tc[12];
+    for (int k = 0; k < 12; k++) {
+        Tc[k] = __fmaf_rn(beta, p1[k] - pose[k], pose[k]);
+        if (!(fabsf(Tc[k]) <= 3.4028234e38f)) return;
+    }
+    pose[kPoseBeta] = beta;
+    pose[kPoseOff] = beta * step;
+    for (int k = 0; k < 12; k++) pose[kPoseC + k] = hist[k] = Tc[k];
+}
+
 
 // One thread: solve the 3x3 problem of acc, T <- dT * T (device pose), stats as in pcp.h
 // (the host loop of pcp_icp_run, minus the convergence test).  A failed solve latches
@@ -1716,6 +1835,13 @@ __global__ void k_icp_solve_dev(const double* acc, int do_scale, double* T, doub
 // per-wave search segments, octant search of that list (`oct`), concatenate the fallback segments,
 // exact fallback.  `a` carries oct_g and ring_g; its partials end at the fallback pass's.
 using OctKernel = void (*)(IcpArgs, const int32_t*, const uint32_t*);
+// the dense first launch in its look-ahead form (after a pilot step): waves per SIMD and its grid
+// (6 waves/SIMD: 80 VGPRs and 144 B of scratch against 128 VGPRs and none at 4, but measured 0.11 ms
+// faster on the 50M first launch; the list launches of the same form stay at 4)
+#ifndef PCP_OCT_WAVES_LOOK0
+#define PCP_OCT_WAVES_LOOK0 6
+#endif
+int nb_look0(const pcp_icp* icp) { return PCP_OCT_WAVES_LOOK0 < PCP_OCT_WAVES ? icp->nb_fast_l : icp->nb_fast; }
 int icp_chain(pcp_icp* icp, hipStream_t st, IcpArgs& a, OctKernel oct) {
     pcp_ctx* ctx = icp->ctx;
     uint32_t* const svc_n = icp->sv_off + a.nseg_v;  // the two lists' lengths follow their segments' offsets
@@ -1739,7 +1865,7 @@ int icp_chain(pcp_icp* icp, hipStream_t st, IcpArgs& a, OctKernel oct) {
 
 // T (host) or T_dev (device pose, read by k_pose_from_T) -- exactly one is non-null
 int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, int32_t* corr_idx,
-               float* corr_d2, const double* T_dev = nullptr, IcpArgs* args_out = nullptr) {
+               float* corr_d2, const double* T_dev = nullptr, IcpArgs* args_out = nullptr, bool pilot_ok = true) {
     pcp_ctx* ctx = icp->ctx;
     const pcp_index* tg = icp->target;
     IcpArgs a{};
@@ -1813,6 +1939,7 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     }
     PCP_HIP(ctx, hipEventRecord(e0, ctx->stream));
     const bool verify = a.g.dense && icp->launches > 0;  // the first launch has nothing cached
+    icp->has_pred = icp->has_pred && icp->launches == 0;  // (a prediction serves the first launch only)
     icp->last_verified = verify;
     // the search lists: the look-ahead form unless it is switched off (beta = 0: T_c = T_t).  Launch
     // 1 has no step ratio yet, so beta = 0 there too, and the plain form is the faster one on its
@@ -1858,16 +1985,46 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
         if (graph && icp->gexec) PCP_HIP(ctx, hipGraphLaunch(icp->gexec, ctx->stream));
         else PCP_TRY(icp_chain(icp, ctx->stream, a, oct_list));
     } else {
-        // the first launch (nothing cached: the octant search takes every query, beta = 0, the plain
-        // form) or a sparse grid (the fallback pass takes every query)
+        // the first launch (nothing cached: the octant search takes every query) or a sparse grid
+        // (the fallback pass takes every query)
         const int nb_idle = a.g.dense ? icp->nb_ver : icp->nb_ver + icp->nb_fast;
         PCP_HIP(ctx, hipMemsetAsync(part_v, 0, (size_t)nb_idle * kAcc * sizeof(double), ctx->stream));
         if (a.g.dense) {
             if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_ver, ctx->stream));
             a.partials = part_o;
             a.oct_g = icp->oct_g_first;
+            // The handle's first launch can look ahead too: a predicted second pose -- the caller's
+            // (pcp_icp_predict_first), or by default on a large handle one Kabsch step over a sample
+            // of the queries (the pilot) -- gives beta_0 and T_c (k_pilot_map).  beta_0 is known on
+            // the device only, so both forms of the search are enqueued and the one it did not
+            // choose exits at once: beta_0 = 0 runs exactly the plain first launch.
+            const bool pilot = pilot_ok && !icp->has_pred && !icp->no_pilot && !icp->dbg && icp->nq > 0 &&
+                               (icp->pilot_always || icp->nq >= kPilotMinQueries);
+            const bool look0 = icp->launches == 0 && !icp->no_look && (icp->has_pred || pilot);
+            if (look0) {
+                PilotPred pred{};
+                if (icp->has_pred) {
+                    pred.on = 1;
+                    for (int k = 0; k < 16; k++) pred.T1[k] = icp->pred[k];
+                } else {
+                    const int64_t nch = (icp->nq + 63) / 64;
+                    a.pilot_stride = std::max<int64_t>(1, nch / kPilotChunks);
+                    const int64_t nsamp = (nch + a.pilot_stride - 1) / a.pilot_stride;
+                    const int nbp = (int)std::min<int64_t>((nsamp + kOctW - 1) / kOctW, icp->nb_fast);
+                    hipLaunchKernelGGL(k_icp_pilot, dim3(nbp), dim3(kIcpBlock), 0, ctx->stream, a, nsamp);
+                    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kAcc * kRedGroups), 0, ctx->stream,
+                                       (const double*)part_o, nbp, icp->pilot_acc, (const uint32_t*)nullptr);
+                }
+                hipLaunchKernelGGL(k_pilot_map, dim3(1), dim3(1), 0, ctx->stream, (const double*)icp->pilot_acc, pred,
+                                   la, icp->pose_dev, icp->pose_hist);
+                a.when_beta = 1;
+                hipLaunchKernelGGL((k_icp_octant<PCP_OCT_WAVES_LOOK0, true>), dim3(nb_look0(icp)), dim3(kIcpBlock), 0,
+                                   ctx->stream, a, (const int32_t*)nullptr, (const uint32_t*)nullptr);
+                a.when_beta = 2;
+            }
             hipLaunchKernelGGL((k_icp_octant<PCP_OCT_WAVES, false>), dim3(icp->nb_fast), dim3(kIcpBlock), 0,
                                ctx->stream, a, (const int32_t*)nullptr, (const uint32_t*)nullptr);
+            a.when_beta = 0;
         }
         if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_mid, ctx->stream));
         if (a.g.dense) {  // compact the per-wave fallback segments into one list
@@ -2085,6 +2242,7 @@ int icp_make(pcp_ctx* ctx, const pcp_index* target, QXyz* q3, int32_t* qi, int64
     icp->nseg_v = nwaves_v;
     int rc = dmalloc(ctx, &icp->partials, (size_t)(icp->nb_ver + icp->nb_fast + icp->nb_ring) * kAcc);
     if (!rc) rc = dmalloc(ctx, &icp->acc, kAcc);
+    if (!rc) rc = dmalloc(ctx, &icp->pilot_acc, kAcc);
     // 24 pose floats, the launch index, the look-ahead state and map (kPoseStep .. kPoseWords)
     if (!rc) rc = dmalloc(ctx, &icp->pose_dev, kPoseWords);
     // 12-byte cache records when every position (and the far sentinel) fits 26 bits
@@ -2226,9 +2384,12 @@ int pcp_icp_set_options(pcp_icp* icp, int oct_lanes_first, int oct_lanes_list, i
     icp->oct_g_first = oct_lanes_first ? oct_lanes_first : 1;
     icp->oct_g_list = oct_lanes_list;
     icp->ring_g = ring_lanes;
-    icp->dbg = ablate & ~(PCP_ICP_OPT_WIDE_CACHE | PCP_ICP_OPT_GRAPH | PCP_ICP_OPT_NO_LOOKAHEAD);
+    icp->dbg = ablate & ~(PCP_ICP_OPT_WIDE_CACHE | PCP_ICP_OPT_GRAPH | PCP_ICP_OPT_NO_LOOKAHEAD |
+                          PCP_ICP_OPT_NO_PILOT | PCP_ICP_OPT_PILOT_ALWAYS);
     icp->graph = (ablate & PCP_ICP_OPT_GRAPH) != 0;
     icp->no_look = (ablate & PCP_ICP_OPT_NO_LOOKAHEAD) != 0;
+    icp->no_pilot = (ablate & PCP_ICP_OPT_NO_PILOT) != 0;
+    icp->pilot_always = (ablate & PCP_ICP_OPT_PILOT_ALWAYS) != 0;
     return PCP_OK;
 }
 
@@ -2243,6 +2404,7 @@ int pcp_icp_destroy(pcp_icp* icp) {
     pcp::dfree(icp->owner, icp->qidx);
     pcp::dfree(icp->owner, icp->partials);
     pcp::dfree(icp->owner, icp->acc);
+    pcp::dfree(icp->owner, icp->pilot_acc);
     pcp::dfree(icp->owner, icp->cand);
     pcp::dfree(icp->owner, icp->pose_hist);
     pcp::dfree(icp->owner, icp->sv);
@@ -2310,7 +2472,8 @@ static int icp_keys(pcp_ctx* ctx, pcp_icp* icp, const double* T, const double* T
     const int saved = icp->dbg;
     icp->dbg |= pcp::kDbgNoAccum;  // correspondences only
     pcp::IcpArgs a{};
-    const int rc = pcp::icp_launch(icp, T, rmax, icp->acc, nullptr, nullptr, T_dev, &a);
+    // (the loops built on the keys minimise something else: no pilot step for them)
+    const int rc = pcp::icp_launch(icp, T, rmax, icp->acc, nullptr, nullptr, T_dev, &a, false);
     icp->dbg = saved;
     PCP_TRY(rc);
     if (icp->nq_in > icp->nq)
@@ -2509,6 +2672,30 @@ int pcp_icp_last_lookahead(const pcp_icp* icp, double* beta, double* max_offset_
     PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (beta) *beta = w[0];
     if (max_offset_m) *max_offset_m = w[1];
+    return PCP_OK;
+}
+
+int pcp_icp_predict_first(pcp_icp* icp, const double T1[16]) {
+    if (!icp || !T1) return PCP_ERR_ARG;
+    if (icp->launches > 0)
+        return pcp::set_error(icp->owner, PCP_ERR_ARG, "pcp_icp_predict_first only before the handle's first launch");
+    std::memcpy(icp->pred, T1, sizeof(icp->pred));
+    icp->has_pred = true;
+    return PCP_OK;
+}
+
+int pcp_icp_pilot_info(const pcp_icp* icp, int64_t* stride, int64_t* chunks, int64_t* pairs) {
+    if (!icp || !icp->ctx) return PCP_ERR_ARG;
+    pcp_ctx* ctx = icp->ctx;
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    float w = -1.f;
+    PCP_HIP(ctx, hipMemcpyAsync(&w, icp->pose_dev + pcp::kPilotPairs, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const bool ran = icp->launches > 0 && w >= 0.f;
+    const int64_t nch = (icp->nq + 63) / 64, s = std::max<int64_t>(1, nch / pcp::kPilotChunks);
+    if (stride) *stride = ran ? s : 0;
+    if (chunks) *chunks = ran ? (nch + s - 1) / s : 0;
+    if (pairs) *pairs = ran ? (int64_t)w : -1;
     return PCP_OK;
 }
 

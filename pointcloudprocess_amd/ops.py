@@ -357,17 +357,21 @@ class ICP:
     WIDE_CACHE = 128  # PCP_ICP_OPT_WIDE_CACHE
     GRAPH = 256       # PCP_ICP_OPT_GRAPH
     NO_LOOKAHEAD = 512  # PCP_ICP_OPT_NO_LOOKAHEAD
+    NO_PILOT = 1024     # PCP_ICP_OPT_NO_PILOT
+    PILOT_ALWAYS = 2048  # PCP_ICP_OPT_PILOT_ALWAYS
 
     def set_options(self, oct_lanes_first=1, oct_lanes_list=0, ring_lanes=0, ablate=0, wide_cache=False,
-                    graph=False, lookahead=True):
+                    graph=False, lookahead=True, pilot=None):
         """Test / profiling controls (pcp_icp_set_options): lanes per query of the octant pass
         (first launch, later lists; 0 = by density) and of the fallback pass (0 = by length);
         `ablate` switches passes off (results are then wrong); `wide_cache` keeps 16-byte cache
         records (before the first step); `graph` replays one captured HIP graph per device-pose
         launch; `lookahead=False` searches around the query itself instead of ahead on its path
-        (results are identical in all three cases)."""
+        (results are identical in all three cases); `pilot`: the pilot step before the first launch,
+        None = by the handle's size, True = always, False = never (results are identical)."""
         flags = (int(ablate) | (self.WIDE_CACHE if wide_cache else 0) | (self.GRAPH if graph else 0) |
-                 (0 if lookahead else self.NO_LOOKAHEAD))
+                 (0 if lookahead else self.NO_LOOKAHEAD) |
+                 (0 if pilot is None else (self.PILOT_ALWAYS if pilot else self.NO_PILOT)))
         self.ctx.check(self.ctx.lib.pcp_icp_set_options(self.h, int(oct_lanes_first), int(oct_lanes_list),
                                                         int(ring_lanes), flags))
 
@@ -509,6 +513,18 @@ class ICP:
         n = C.c_int64()
         self.ctx.check(self.ctx.lib.pcp_icp_last_fallback(self.h, C.byref(n)))
         return n.value
+
+    def predict_first(self, T1):
+        """The caller's prediction of the second launch's pose (before the first launch): the first
+        launch looks ahead towards it and no pilot step runs (pcp_icp_predict_first)."""
+        Tm = _lib.f64arr(np.asarray(T1, dtype=np.float64).reshape(16))
+        self.ctx.check(self.ctx.lib.pcp_icp_predict_first(self.h, Tm))
+
+    def pilot_info(self):
+        """(stride, sampled chunks, pairs) of the first launch's pilot step; (0, 0, -1): none ran."""
+        s, c, n = C.c_int64(), C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.pcp_icp_pilot_info(self.h, C.byref(s), C.byref(c), C.byref(n)))
+        return s.value, c.value, n.value
 
     def close(self):
         if getattr(self, "h", None):
