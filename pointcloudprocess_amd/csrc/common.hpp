@@ -99,13 +99,16 @@ int dmalloc(pcp_ctx* ctx, T** p, size_t count) {
     return rc;
 }
 
-// Device temporaries of one call.  get() takes a block from ctx's cache and the destructor gives
-// back whatever is still held, so no return path leaks.  The cache serves later requests of the
-// same call from freed blocks: a temporary that is dead before a later allocation is returned
-// there with free(), not left to scope exit, or the call's peak footprint grows.
+// One owner for device blocks and timing events: the temporaries of one call, or everything an ICP
+// handle keeps (icp_handle.hpp).  get() takes a block from ctx's cache, event() an event from its
+// pool, and the destructor gives back whatever is still held, so no return path leaks.  The cache
+// serves later requests of the same call from freed blocks: a temporary that is dead before a later
+// allocation is returned there with free(), not left to scope exit, or the call's peak footprint
+// grows.
 struct Tmp {
     pcp_ctx* ctx;
     std::vector<void*> held;
+    std::vector<hipEvent_t> events;
     explicit Tmp(pcp_ctx* c) : ctx(c) {}
     Tmp(const Tmp&) = delete;
     Tmp& operator=(const Tmp&) = delete;
@@ -115,6 +118,17 @@ struct Tmp {
         PCP_TRY(dmalloc(ctx, p, count));
         held.push_back((void*)*p);
         return PCP_OK;
+    }
+    hipError_t event(hipEvent_t* ev) {
+        const hipError_t e = event_get(ctx, ev);
+        if (e == hipSuccess) events.push_back(*ev);
+        return e;
+    }
+    // take over a block of ctx's cache that another guard released
+    template <typename T>
+    T* adopt(T* p) {
+        held.push_back((void*)p);
+        return p;
     }
     // hand a block over to a longer-lived owner: the guard no longer frees it
     template <typename T>
@@ -132,6 +146,8 @@ struct Tmp {
     void free_all() {
         for (void* p : held) dfree(ctx, p);
         held.clear();
+        for (hipEvent_t ev : events) event_put(ctx, ev);
+        events.clear();
     }
 };
 
@@ -160,8 +176,9 @@ __device__ __forceinline__ bool finite3(double x, double y, double z) {
 int seqfold_aos48(pcp_ctx* ctx, const void* p0, int64_t n0, const void* p1, int64_t n1, int is_dense,
                   double s_host[4]);
 
-// What code outside icp.hip may know of an ICP handle (icp.hip): its target index and the number
-// of queries passed to pcp_icp_create (the length of a pcp_icp_keys_dev buffer).
+// What code that does not include icp_handle.hpp may know of an ICP handle (icp_create.hip): its
+// target index and the number of queries passed to pcp_icp_create (the length of a pcp_icp_keys_dev
+// buffer).
 const pcp_index* icp_target(const pcp_icp* icp);
 int64_t icp_query_count(const pcp_icp* icp);
 

@@ -9,149 +9,22 @@
 // fixed-order pass over the workgroup partials.  The host solves the 3x3 Kabsch/Umeyama
 // problem (pcp_icp_solve) and composes the pose.
 //
-// Owned here: the handle, the search kernels and their caches, the look-ahead pose block, the 3x3
-// solve, and the loops of the target-sharded key kernels (k_make_keys, k_acc_keys, k_acc_owned).
+// Owned here: the search kernels and their caches, the launch (icp_args, icp_fallback, icp_chain,
+// icp_launch), k_make_keys, and the step, run, keys and getter entry points.  The handle is
+// icp_handle.hpp's, its creation icp_create.hip's, the pose block's kernels icp_pose.hpp's, the 3x3
+// solve icp_solve.hpp's and the loops over exchanged keys icp_shard.hip's.
 // The search arithmetic is icp_search.hpp's; the key's layout, the pose cast, the Kabsch terms of
 // a pair and the block reductions of the key kernels are icp_pair.hpp's.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <vector>
 
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include "sortcfg.hpp"
-
-#include "icp_pair.hpp"
+#include "icp_handle.hpp"
+#include "icp_pose.hpp"
 #include "wave_acc.hpp"
 
 namespace pcp {
-// a sorted query's coordinates: 12 bytes (one global_load_dwordx3 per lane)
-struct QXyz {
-    float x, y, z;
-};
-}  // namespace pcp
-
-struct pcp_icp {
-    pcp_ctx* ctx = nullptr;       // the context of the last call (launches go to its stream)
-    pcp_ctx* owner = nullptr;     // the creating context: owns the buffers (a lifetime reference)
-    const pcp_index* target = nullptr;
-    int64_t nq = 0;               // finite queries
-    int64_t nq_in = 0;            // queries passed to pcp_icp_create
-    pcp::QXyz* q = nullptr;       // sorted queries, 12-byte xyz (the verify stream reads 12 B, not 16)
-    int32_t* qidx = nullptr;      // their original indices (read only for caller-order outputs)
-    uint32_t* cand = nullptr;     // per sorted query: its cache record (cache_load / cache_store): the
-                                  // sorted-target positions of its 3 nearest targets at its last search
-                                  // (the winner is always among them), the launch slot s of that search
-                                  // and D, a lower bound on the distance from the query, at that launch's
-                                  // pose, to every target NOT cached.  12 bytes when the target has fewer
-                                  // than 2^26 - 2 points (narrow), else 16
-    bool narrow = false;
-    float* pose_hist = nullptr;   // 256 x 12 floats: the pose of launch t at slot t & hist_mask
-    int64_t launches = 0;         // correspondence launches so far (the first has nothing to verify)
-    bool last_verified = false;   // the last launch ran the verify pass
-    int32_t* sv = nullptr;        // verify pass: per-wave segments of uncertified queries (sv_seg each)
-    uint32_t* sv_count = nullptr;
-    uint32_t* sv_off = nullptr;   // [nseg_v]: the search list's length (k_list_compact)
-    int32_t* svc = nullptr;       // compacted search list
-    int64_t sv_seg = 0;
-    int64_t nseg_v = 0;           // verify list segments: one per wave, or one per chunk (XCD split)
-    int nb_ver = 0;
-    int32_t* fb = nullptr;        // fallback lists: one segment of fb_seg entries per octant WG
-    uint32_t* fb_count = nullptr; // per octant wave: entries in its segment
-    uint32_t* fb_off = nullptr;   // [nseg]: the fallback list's length (k_list_compact)
-    int32_t* fbc = nullptr;       // compacted fallback list
-    int64_t fb_seg = 0;
-    double* partials = nullptr;   // (nb_ver + nb_fast + nb_ring) * 24
-    double* acc = nullptr;        // 24 (scratch for pcp_icp_run)
-    int nb_fast = 0, nb_ring = 0;
-    int nb_fast_l = 0;            // octant grid of the list launches (<= nb_fast)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr, ev_ver = nullptr;
-    float* pose_dev = nullptr;    // 24 floats: this launch's pose (R row-major, t), then the previous one
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;  // per-launch timing events (device loop)
-    size_t ntev = 0;              // pairs recorded since the last pcp_icp_kernel_ms
-    int dbg = 0;                  // ablation flags (pcp_icp_set_options; profiling only: results are wrong)
-    int oct_g_first = 1;          // lanes per query of the octant pass: first launch (all queries)
-    int oct_g_list = 0;           // ... and the verify pass's search lists (0: by the list's density)
-    int ring_g = 0;               // lanes per query of the fallback pass, 0 = by the list's length
-    double last_ms = 0.0;
-    int last_launches = 0;
-    uint32_t last_fallback = 0;
-    uint32_t last_searched = 0;   // queries the verify pass could not certify (searched)
-    hipGraphExec_t gexec = nullptr;  // the verify .. fallback section of a device-pose launch (icp_launch)
-    float graph_r2 = 0.f;            // the rmax^2 it was captured with
-    bool graph_off = false;          // capture failed: plain launches
-    bool graph = false;              // PCP_ICP_OPT_GRAPH
-    bool no_look = false;            // PCP_ICP_OPT_NO_LOOKAHEAD: beta = 0, the plain search kernels
-    bool no_pilot = false;           // PCP_ICP_OPT_NO_PILOT: no pilot step before the first launch
-    bool pilot_always = false;       // PCP_ICP_OPT_PILOT_ALWAYS: the pilot below kPilotMinQueries too
-    bool has_pred = false;           // pcp_icp_predict_first: pred replaces the pilot's estimate
-    double pred[16] = {};            // the caller's predicted second pose
-    double* pilot_acc = nullptr;     // 24: the pilot's reduced accumulators
-};
-
-namespace pcp {
 namespace {
-
-constexpr int kIcpBlock = 256;
-#ifndef PCP_OCT_WAVES_LIST  // the octant pass over the verify pass's lists: more registers, fewer waves
-#define PCP_OCT_WAVES_LIST 4
-#endif
-#ifndef PCP_OCT_WAVES
-#define PCP_OCT_WAVES 6
-#endif
-#ifndef PCP_VER_WAVES   // verify (per-lane accumulators: ~100 VGPRs)
-#define PCP_VER_WAVES 4
-#endif
-
-#ifndef PCP_RING_WAVES
-#define PCP_RING_WAVES 6
-#endif
-
-struct IcpArgs {
-    GridDesc g;
-    const float4* tp;   // sorted target points
-    const QXyz* q;      // sorted queries (xyz)
-    const int32_t* qidx;  // their original indices
-    int64_t nq;
-    int64_t nchunks;
-    float R[9], t[3];
-    float Rp[9], tq[3]; // the previous launch's pose (verify pass)
-    float Rc[9], tc[3]; // the look-ahead map T_c of this launch (k_pose_set): where the searches centre
-    float r2;
-    float cert2;        // certified radius^2 of the 2x2x2 octant search
-    float rho;          // octant half-width in cell units (0.5 - margin)
-    float mc;           // cell-unit margin for pruning
-    double* partials;
-    uint32_t* cand;     // cache records (cache_load / cache_store)
-    int narrow;         // 12-byte records
-    uint32_t hist_mask; // pose history slot of a launch: launch & hist_mask (63 narrow, 255 wide)
-    uint32_t max_age;   // older caches are searched again (so their slot is never reused)
-    float dunit, inv_dunit;  // narrow D code unit (cell size / 1024)
-    const float* pose_hist;
-    uint32_t launch;    // this launch's index (mod 2^32)
-    uint32_t ntp;       // target points (tp[ntp] is the far sentinel)
-    int32_t* sv;        // verify pass output segments (sv_seg entries per wave)
-    uint32_t* sv_count;
-    uint32_t* sv_off;
-    int64_t sv_seg;
-    int64_t nseg_v;     // verify-pass waves
-    int32_t* fb;
-    uint32_t* fb_count;
-    uint32_t* fb_off;   // [nseg]: the compacted fallback list's length
-    int64_t fb_seg;
-    int nb_fast;
-    int64_t nseg;       // fallback segments (= waves of the octant kernel)
-    int ring_all;       // ring kernel: process every query (sparse grid) instead of the list
-    int dbg;            // ablation flags (pcp_icp_set_options; profiling only)
-    int oct_g;          // octant pass lanes per query: 1, 2, 4, 8, or 0 = by the list's density
-    int ring_g;         // fallback pass lanes per query: 1, 2, 4, 8, or 0 = by the list's length
-    const float* pose;  // device poses (current, previous: 24 floats) overriding R/t, Rp/tq, or null
-    const uint32_t* launch_dev;  // device copy of `launch` (k_pose_set), so a captured launch graph replays
-    int when_beta;      // first launch after a pilot: 1 = run only if the pose block's beta > 0, 2 = only
-                        // if it is 0 (the look-ahead and the plain kernel are both enqueued), 0 = always
-    int64_t pilot_stride;  // k_icp_pilot: every pilot_stride-th 64-query chunk is sampled
-};
 
 // sorted query i as {x, y, z, 0}
 __device__ __forceinline__ float4 ldq(const IcpArgs& a, int64_t i) {
@@ -159,29 +32,25 @@ __device__ __forceinline__ float4 ldq(const IcpArgs& a, int64_t i) {
     return make_float4(v.x, v.y, v.z, 0.f);
 }
 
-// the pose as the kernels use it: from the device copy when the loop is device-resident
+// The pose and the launch index as the kernels use them: from the handle's pose block.  The test is
+// never false (icp_args always sets a.pose).  It is kept for the code it makes: without it the
+// register allocation of the search kernels shifts and k_icp_ring takes one more spill slot (36 ->
+// 40 B of scratch; profiles/icp_split/stage2_regs.txt).
 __device__ __forceinline__ void load_pose(IcpArgs& a) {
-    if (a.launch_dev) a.launch = *a.launch_dev;
     if (a.pose) {
+        a.launch = a.pose->launch;
 #pragma unroll
-        for (int k = 0; k < 9; k++) a.R[k] = a.pose[k];
+        for (int k = 0; k < 9; k++) a.R[k] = a.pose->cur[k];
 #pragma unroll
-        for (int k = 0; k < 3; k++) a.t[k] = a.pose[9 + k];
+        for (int k = 0; k < 3; k++) a.t[k] = a.pose->cur[9 + k];
     }
 }
-// the look-ahead map (pose block words kPoseC ..): equal to the pose when beta = 0
-constexpr int kPoseStep = 25, kPoseBeta = 26, kPoseOff = 27, kPoseC = 28, kPoseWords = 41;
+// the look-ahead map: equal to the pose when beta = 0
 __device__ __forceinline__ void load_pose_c(IcpArgs& a) {
 #pragma unroll
-    for (int k = 0; k < 9; k++) a.Rc[k] = a.pose[kPoseC + k];
+    for (int k = 0; k < 9; k++) a.Rc[k] = a.pose->c[k];
 #pragma unroll
-    for (int k = 0; k < 3; k++) a.tc[k] = a.pose[kPoseC + 9 + k];
-}
-__device__ __forceinline__ void load_prev_pose(IcpArgs& a) {
-#pragma unroll
-    for (int k = 0; k < 9; k++) a.Rp[k] = a.pose[12 + k];
-#pragma unroll
-    for (int k = 0; k < 3; k++) a.tq[k] = a.pose[21 + k];
+    for (int k = 0; k < 3; k++) a.tc[k] = a.pose->c[9 + k];
 }
 
 // Ablation switches for profiling (pcp_icp_set_options, PCP_ICP_ABLATE_*); results are wrong
@@ -193,15 +62,7 @@ constexpr int kDbgNoScan = PCP_ICP_ABLATE_NO_SCAN, kDbgNoAccum = PCP_ICP_ABLATE_
 // look-ahead map: the search centre c (the verify pass rebuilds exactly this from the launch's
 // history slot)
 __device__ __forceinline__ void xform_c(const IcpArgs& a, const float4 q, float& x, float& y, float& z) {
-    x = __fmaf_rn(a.Rc[2], q.z, __fmaf_rn(a.Rc[1], q.y, __fmaf_rn(a.Rc[0], q.x, a.tc[0])));
-    y = __fmaf_rn(a.Rc[5], q.z, __fmaf_rn(a.Rc[4], q.y, __fmaf_rn(a.Rc[3], q.x, a.tc[1])));
-    z = __fmaf_rn(a.Rc[8], q.z, __fmaf_rn(a.Rc[7], q.y, __fmaf_rn(a.Rc[6], q.x, a.tc[2])));
-}
-// the same expression under the previous launch's pose
-__device__ __forceinline__ void xform_prev(const IcpArgs& a, const float4 q, float& x, float& y, float& z) {
-    x = __fmaf_rn(a.Rp[2], q.z, __fmaf_rn(a.Rp[1], q.y, __fmaf_rn(a.Rp[0], q.x, a.tq[0])));
-    y = __fmaf_rn(a.Rp[5], q.z, __fmaf_rn(a.Rp[4], q.y, __fmaf_rn(a.Rp[3], q.x, a.tq[1])));
-    z = __fmaf_rn(a.Rp[8], q.z, __fmaf_rn(a.Rp[7], q.y, __fmaf_rn(a.Rp[6], q.x, a.tq[2])));
+    xform_rt(a.Rc, a.tc, q, x, y, z);
 }
 
 // min / max of non-NaN floats as one v_med3_f32 (fminf/fmaxf add canonicalizing v_max ops)
@@ -348,8 +209,6 @@ struct CacheRec {
     uint32_t slot;        // launch of the search & hist_mask
     float D;
 };
-constexpr uint32_t kPos26 = (1u << 26) - 1;
-constexpr int kHist = 256;  // pose history slots allocated (narrow records use 64 of them)
 __device__ __forceinline__ uint32_t dcode12(float D, float inv_unit) {
     const float x = D * inv_unit;
     if (!(x >= 1.f)) return 0u;
@@ -1179,7 +1038,7 @@ template <int MINW, bool LOOK>
 __global__ void __launch_bounds__(kIcpBlock, MINW) k_icp_octant(IcpArgs a, const int32_t* list,
                                                                  const uint32_t* list_n) {
     // the first launch after a pilot step: the form that beta_0 (k_pilot_map) did not choose exits
-    if (a.when_beta && (a.pose[kPoseBeta] > 0.f) != (a.when_beta == 1)) return;
+    if (a.when_beta && (a.pose->beta > 0.f) != (a.when_beta == 1)) return;
     load_pose(a);
     if constexpr (LOOK) load_pose_c(a);
     __shared__ double s_acc[kOctW][kAcc];
@@ -1453,420 +1312,12 @@ __global__ void k_make_keys(IcpArgs a, uint32_t offset, uint64_t* keys) {
     }
 }
 
-// accumulators over the queries whose global winner lies in [lo, hi) (this rank's shard);
-// float products are exact in fp64, so only the summation order differs from the oracle
-__global__ void __launch_bounds__(kPairBlock) k_acc_keys(const QXyz* q, const int32_t* qidx, int64_t n,
-                                                         const uint64_t* keys, uint64_t lo, uint64_t hi,
-                                                         const float* shard, size_t stride_f, Pose32 P,
-                                                         double* partials) {
-    double acc[kAcc - 1];
-#pragma unroll
-    for (int k = 0; k < kAcc - 1; k++) acc[k] = 0.0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float4 qq = make_float4(q[i].x, q[i].y, q[i].z, 0.f);
-        const uint64_t key = keys[qidx[i]];
-        if (key == kNoKey) continue;
-        const uint64_t g = key_index(key);
-        if (g < lo || g >= hi) continue;
-        const float* p = shard + (size_t)(g - lo) * stride_f;
-        float x, y, z;
-        xform(P, qq, x, y, z);
-        const double qv[3] = {x, y, z}, pv[3] = {p[0], p[1], p[2]};
-        kabsch_terms(qv, pv, key, acc);
-    }
-    block_partials<kAcc - 1, kAcc>(acc, partials + (int64_t)blockIdx.x * kAcc);
-}
-
-__global__ void __launch_bounds__(kPairBlock) k_sum_partials(const double* part, int nb, double* out) {
-    sum_partials<kAcc>(part, nb, out);
-}
-
-// Target-sharded mode, device-resident form: after a ReduceScatter(MIN) of
-// the per-query keys, each rank knows the global winners of its slice of the queries; the shard
-// that owns each winner (by its global target index) is all-gathered as one byte per query, and
-// every rank accumulates exactly the queries whose winner lies in its own shard, reading the
-// winner from its LOCAL shard -- no rank ever holds the full target.  A SUM over ranks gives the
-// accumulators of every query.
-// owner[i] = s with bounds[s] <= global index < bounds[s + 1], or 255 (no correspondence)
-__global__ void k_keys_owner(const uint64_t* keys, int64_t n, const int64_t* bounds, int nshards, uint8_t* owner) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t k = keys[i];
-        uint8_t o = 255;
-        if (k != kNoKey) {
-            const int64_t g = (int64_t)key_index(k);
-            int lo = 0, hi = nshards;  // the last s with bounds[s] <= g
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (bounds[mid] <= g) lo = mid;
-                else hi = mid;
-            }
-            o = (uint8_t)lo;
-        }
-        owner[i] = o;
-    }
-}
-
-// accumulators of the queries (original order, q) whose winner this rank owns: the winner is
-// the rank's local key's target (its global index less lo) -- for an owned query the local key
-// IS the global MIN.  The pose is pose32 of the device 4x4, the image xform's and the terms
-// kabsch_terms' (icp_pair.hpp), so only the summation order differs from the oracle.
-__global__ void __launch_bounds__(kPairBlock) k_acc_owned(const double* T, const float* q, size_t qs, int64_t n,
-                                                          const uint64_t* keys, const uint8_t* owner, int rank,
-                                                          int64_t lo, int64_t hi, const float* shard, size_t ss,
-                                                          double* partials) {
-    const Pose32 P = pose32(T);
-    double acc[kAcc - 1];
-#pragma unroll
-    for (int k = 0; k < kAcc - 1; k++) acc[k] = 0.0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        if (owner[i] != (uint8_t)rank) continue;
-        const uint64_t key = keys[i];
-        const int64_t g = (int64_t)key_index(key);
-        if (key == kNoKey || g < lo || g >= hi) continue;
-        const float* p = shard + (size_t)(g - lo) * ss;
-        float x, y, z;
-        xform(P, q + (size_t)i * qs, x, y, z);
-        const double qv[3] = {x, y, z}, pv[3] = {p[0], p[1], p[2]};
-        kabsch_terms(qv, pv, key, acc);
-    }
-    block_partials<kAcc - 1, kAcc>(acc, partials + (int64_t)blockIdx.x * kAcc);
-}
-
-// co-partitioned slab guard (one thread): the owned queries' box [b0..b5] = {x0,x1,y0,y1,z0,z1}
-// under the device pose must keep x within [lo, hi] (the slab core widened by the target halo
-// less rmax); the x-extreme of an affine image of a box is at a corner.  Latches flag = 1.
-__global__ void k_slab_guard(const double* T, double b0, double b1, double b2, double b3, double b4, double b5,
-                             double lo, double hi, int* flag) {
-    const double bx[2] = {b0, b1}, by[2] = {b2, b3}, bz[2] = {b4, b5};
-    double mn = INFINITY, mx = -INFINITY;
-    for (int c = 0; c < 8; c++) {
-        const double x = T[0] * bx[c & 1] + T[1] * by[(c >> 1) & 1] + T[2] * bz[c >> 2] + T[3];
-        mn = fmin(mn, x);
-        mx = fmax(mx, x);
-    }
-    if (!(mn >= lo && mx <= hi)) *flag = 1;
-}
-
-// ---- query order (pcp_icp_create): queries sorted once by target-grid cell in brick-major
-// order (8x8x8-cell bricks, cell order inside a brick -- brick order alone measured 5 % slower
-// searches; stable, so input order inside a cell), carried as float4 {x, y, z, bits(index)}
-// through the radix sort; non-finite queries get key query_key_end (after every cell) and
-// are dropped.
-__global__ void k_query_keys(GridDesc g, const float* q, size_t stride_f, int64_t n, uint32_t* key, float4* rec) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float* p = q + (size_t)i * stride_f;
-        const float x = p[0], y = p[1], z = p[2];
-        const bool fin = isfinite(x) && isfinite(y) && isfinite(z);
-        uint32_t k = query_key_end(g);  // past every brick: non-finite queries sort last
-        if (fin) k = query_cell_key(g, x, y, z);
-        key[i] = k;
-        rec[i] = make_float4(x, y, z, __int_as_float((int)i));
-    }
-}
-
-// the sorted {x, y, z, bits(index)} records -> 12-byte xyz + index arrays
-__global__ void k_split_queries(const float4* qs, int64_t n, QXyz* q, int32_t* qi) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float4 v = qs[i];
-        q[i] = QXyz{v.x, v.y, v.z};
-        qi[i] = __float_as_int(v.w);
-    }
-}
-
-// number of finite queries = first position of the sentinel key in the sorted keys
-// (a single-address atomic per wave costs ~9 ms at 50M queries; this costs nothing)
-__global__ void k_first_at_least(const uint32_t* sorted, int64_t n, uint32_t key, unsigned long long* out) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    *out = (unsigned long long)lo;
-}
-
-// ------------------------------------------------------------------ host 3x3 solve
-// One-sided Jacobi SVD of a 3x3 matrix: A = U diag(s) V^T (columns of U, V).
-// (host and device: the device-resident loop solves on the GPU with the same code)
-__host__ __device__ void svd3(const double Ain[9], double U[9], double s[3], double V[9]) {
-    double A[9];
-    for (int i = 0; i < 9; i++) A[i] = Ain[i];
-    for (int i = 0; i < 9; i++) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 60; sweep++) {
-        double off = 0.0;
-        for (int p = 0; p < 2; p++)
-            for (int q = p + 1; q < 3; q++) {
-                double al = 0, be = 0, ga = 0;
-                for (int r = 0; r < 3; r++) {
-                    al += A[3 * r + p] * A[3 * r + p];
-                    be += A[3 * r + q] * A[3 * r + q];
-                    ga += A[3 * r + p] * A[3 * r + q];
-                }
-                if (ga == 0.0 || fabs(ga) <= 1e-300) continue;
-                double conv = fabs(ga) / sqrt(al * be);
-                if (!(conv > 1e-15)) continue;
-                off = fmax(off, conv);
-                double zeta = (be - al) / (2.0 * ga);
-                double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-                for (int r = 0; r < 3; r++) {
-                    double ap = A[3 * r + p], aq = A[3 * r + q];
-                    A[3 * r + p] = c * ap - sn * aq;
-                    A[3 * r + q] = sn * ap + c * aq;
-                    double vp = V[3 * r + p], vq = V[3 * r + q];
-                    V[3 * r + p] = c * vp - sn * vq;
-                    V[3 * r + q] = sn * vp + c * vq;
-                }
-            }
-        if (off < 1e-15) break;
-    }
-    for (int c = 0; c < 3; c++) {
-        double n = 0;
-        for (int r = 0; r < 3; r++) n += A[3 * r + c] * A[3 * r + c];
-        s[c] = sqrt(n);
-    }
-    // order singular values descending (permute U/V columns consistently)
-    int ord[3] = {0, 1, 2};
-    for (int i = 0; i < 3; i++)
-        for (int j = i + 1; j < 3; j++)
-            if (s[ord[j]] > s[ord[i]]) { const int tmp = ord[i]; ord[i] = ord[j]; ord[j] = tmp; }
-    double A2[9], V2[9], s2[3];
-    for (int c = 0; c < 3; c++) {
-        s2[c] = s[ord[c]];
-        for (int r = 0; r < 3; r++) { A2[3 * r + c] = A[3 * r + ord[c]]; V2[3 * r + c] = V[3 * r + ord[c]]; }
-    }
-    for (int i = 0; i < 9; i++) V[i] = V2[i];
-    for (int c = 0; c < 3; c++) s[c] = s2[c];
-    const double tiny = 1e-14 * (s[0] > 0 ? s[0] : 1.0);
-    for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) U[3 * r + c] = s[c] > tiny ? A2[3 * r + c] / s[c] : 0.0;
-    // complete a rank-deficient basis: u2 = u0 x u1 (planar clouds have rank 2)
-    if (!(s[2] > tiny)) {
-        double u0[3] = {U[0], U[3], U[6]}, u1[3] = {U[1], U[4], U[7]};
-        if (!(s[1] > tiny)) {  // rank 1: any unit vector orthogonal to u0
-            double a[3] = {fabs(u0[0]) < 0.9 ? 1.0 : 0.0, fabs(u0[0]) < 0.9 ? 0.0 : 1.0, 0.0};
-            double d = a[0] * u0[0] + a[1] * u0[1] + a[2] * u0[2];
-            for (int r = 0; r < 3; r++) u1[r] = a[r] - d * u0[r];
-            double nn = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-            for (int r = 0; r < 3; r++) { u1[r] /= nn; U[3 * r + 1] = u1[r]; }
-        }
-        double u2[3] = {u0[1] * u1[2] - u0[2] * u1[1], u0[2] * u1[0] - u0[0] * u1[2], u0[0] * u1[1] - u0[1] * u1[0]};
-        for (int r = 0; r < 3; r++) U[3 * r + 2] = u2[r];
-    }
-}
-
-__host__ __device__ double det3(const double M[9]) {
-    return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) +
-           M[2] * (M[3] * M[7] - M[4] * M[6]);
-}
-
 }  // namespace
 
-// device poses for the kernels: pose[12..23] <- pose[0..11] (the previous launch's), then
-// pose[0..11] <- R, t of T_dev (row-major 4x4 doubles cast to fp32, as on the host) or of the
-// host-cast hp (pose32) when T_dev is null
-// The look-ahead map.  ICP steps are almost collinear and shrink geometrically (ratio r per
-// launch), so a query's remaining path from q_t is about (q_t - q_{t-1}) r / (1 - r) along the
-// last step.  A search centred at c = T_c q, T_c = T_t + beta (T_t - T_{t-1}) with
-// beta = alpha r / (1 - r), puts the cached ball around the path still to come instead of around
-// its start.  T_c is an affine map, written to this launch's history slot (where the verify pass
-// rebuilds c) and beside the pose (where the search kernels read it).  Exactness never depends on
-// it: the certificate holds for any centre; beta only decides how many later searches there are.
-// The step's size is its largest displacement over the corners of `box`, the target grid's box
-// grown by rmax (it holds every query that can have a correspondence); beta = 0 at the second
-// launch (no ratio yet), when the step did not shrink (a pose jump included), and it is cut so
-// that no corner's offset exceeds cap.  The first launch has no step behind it at all: its beta
-// comes from a predicted second pose (the pilot step or the caller's, k_pilot_map), else it is 0.
-struct LookAhead {
-    float lo[3], hi[3];  // the box
-    float alpha, cap;    // fraction of the predicted remaining path; largest offset (m)
-    int off;             // PCP_ICP_OPT_NO_LOOKAHEAD
-};
-#ifndef PCP_LOOK_ALPHA
-#define PCP_LOOK_ALPHA 0.5f
-#endif
-constexpr float kLookAlpha = PCP_LOOK_ALPHA, kLookCap = 0.02f, kLookRmax = 0.9f;
-// The first launch's look-ahead (k_pilot_map): beta_0 = min(kPilotAlpha, kPilotCap / s_1) with s_1
-// the predicted first step's size.  The first step is the largest of the registration and the
-// second is still large, so the centre goes further than one step when the cap allows
-// (tools/sim_icp_pilot.py sweeps both).
-#ifndef PCP_PILOT_ALPHA
-#define PCP_PILOT_ALPHA 1.5f
-#endif
-#ifndef PCP_PILOT_CAP
-#define PCP_PILOT_CAP 0.045f
-#endif
-constexpr float kPilotAlpha = PCP_PILOT_ALPHA, kPilotCap = PCP_PILOT_CAP;
-constexpr int64_t kPilotChunks = 8192;  // the pilot samples about this many 64-query chunks
-// the pilot runs by default from this many queries: its cost is about constant (three launches and
-// ~8K chunks, ~0.06 ms), below 5 % of a first launch that takes ~44 us per million queries
-constexpr int64_t kPilotMinQueries = (int64_t)1 << 25;
-constexpr int kPilotPairs = 40;  // pose block word: the pilot's pair count (float), -1 = no pilot ran
-
-// the size of the step from pose `prev` to pose `cur` (12 floats each: R row-major, t): the largest
-// displacement y - T_prev T_cur^-1 y = y - (M y - v) over the corners y of the box
-__device__ double step_size(const float* cur, const float* prev, const LookAhead& la) {
-    double A[9], B[9], ta[3], tb[3], Ai[9], BA[9], v[3];
-    for (int k = 0; k < 9; k++) { A[k] = cur[k]; B[k] = prev[k]; }
-    for (int k = 0; k < 3; k++) { ta[k] = cur[9 + k]; tb[k] = prev[9 + k]; }
-    const double det = det3(A);
-    Ai[0] = A[4] * A[8] - A[5] * A[7]; Ai[1] = A[2] * A[7] - A[1] * A[8]; Ai[2] = A[1] * A[5] - A[2] * A[4];
-    Ai[3] = A[5] * A[6] - A[3] * A[8]; Ai[4] = A[0] * A[8] - A[2] * A[6]; Ai[5] = A[2] * A[3] - A[0] * A[5];
-    Ai[6] = A[3] * A[7] - A[4] * A[6]; Ai[7] = A[1] * A[6] - A[0] * A[7]; Ai[8] = A[0] * A[4] - A[1] * A[3];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++)
-            BA[3 * r + c] = (B[3 * r] * Ai[c] + B[3 * r + 1] * Ai[3 + c] + B[3 * r + 2] * Ai[6 + c]) / det;
-    for (int r = 0; r < 3; r++) v[r] = BA[3 * r] * ta[0] + BA[3 * r + 1] * ta[1] + BA[3 * r + 2] * ta[2] - tb[r];
-    double s2 = 0.0;
-    for (int c = 0; c < 8; c++) {
-        const double y[3] = {c & 1 ? la.hi[0] : la.lo[0], c & 2 ? la.hi[1] : la.lo[1], c & 4 ? la.hi[2] : la.lo[2]};
-        double d2 = 0.0;
-        for (int r = 0; r < 3; r++) {
-            const double d = y[r] - (BA[3 * r] * y[0] + BA[3 * r + 1] * y[1] + BA[3 * r + 2] * y[2]) + v[r];
-            d2 += d * d;
-        }
-        s2 = fmax(s2, d2);
-    }
-    return sqrt(s2);
-}
-
-__global__ void k_pose_set(const double* T, Pose32 hp, LookAhead la, float* pose, float* hist, uint32_t launch) {
-    *(uint32_t*)(pose + 24) = launch;
-    for (int k = 0; k < 12; k++) pose[12 + k] = pose[k];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) pose[3 * r + c] = T ? (float)T[4 * r + c] : hp.R[3 * r + c];
-        pose[9 + r] = T ? (float)T[4 * r + 3] : hp.t[r];
-    }
-    // this step's displacement of a point y (target frame)
-    const float step = launch > 0 ? (float)step_size(pose, pose + 12, la) : 0.f, prev = pose[kPoseStep];
-    float beta = 0.f;
-    // launch 1 has no previous step, so no ratio and no look-ahead; launch 0's comes from the pilot
-    // step, if there is one (k_pilot_map overwrites the words written here)
-    const float ratio = launch == 1 ? 0.f : (prev > 0.f ? step / prev : 0.f);
-    if (!la.off && launch > 0 && step > 0.f && ratio > 0.f && ratio < 1.f) {  // (false for a NaN)
-        const float r = fminf(ratio, kLookRmax);
-        beta = la.alpha * r / (1.f - r);
-        if (beta * step > la.cap) beta = la.cap / step;
-    }
-    pose[kPoseStep] = step;
-    pose[kPoseBeta] = beta;
-    pose[kPoseOff] = beta * step;
-    if (launch == 0) pose[kPilotPairs] = -1.f;
-    // T_c: beta = 0 gives the pose itself, bit for bit
-    for (int k = 0; k < 12; k++) pose[kPoseC + k] = __fmaf_rn(beta, pose[k] - pose[12 + k], pose[k]);
-    for (int k = 0; k < 12; k++) hist[k] = pose[kPoseC + k];
-}
-
-__host__ __device__ int icp_solve(const double acc[24], int do_scale, double dT[16]);
-
-// The first launch's look-ahead map, after k_pose_set(launch 0) and before the first search.  One
-// thread.  The predicted second pose T_1 is the caller's (pred.on: pcp_icp_predict_first) or one
-// Kabsch step (no scale) over the pilot's sums, dT * T_0 with T_0 the fp32 pose of the block; then
-// beta_0 = min(kPilotAlpha, kPilotCap / s_1), s_1 the step's size as in k_pose_set, and
-// T_c = T_0 + beta_0 (T_1 - T_0) goes to the pose block and to history slot 0.  A refused solve
-// (fewer than 3 pairs, non-finite sums), a non-finite prediction or s_1 = 0 leave beta_0 = 0 and the
-// block as k_pose_set wrote it: the first launch is then the plain one.
-struct PilotPred {
-    int on;
-    double T1[16];
-};
-__global__ void k_pilot_map(const double* acc, PilotPred pred, LookAhead la, float* pose, float* hist) {
-    double T1[16];
-    if (pred.on) {
-        for (int k = 0; k < 16; k++) T1[k] = pred.T1[k];
-    } else {
-        double a[24], dT[16];
-        for (int k = 0; k < 24; k++) a[k] = acc[k];
-        pose[kPilotPairs] = (float)a[0];
-        if (icp_solve(a, 0, dT) != PCP_OK) return;
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 4; j++) {
-                double v = j == 3 ? dT[4 * i + 3] : 0.0;
-                for (int k = 0; k < 3; k++) v += dT[4 * i + k] * (double)(j == 3 ? pose[9 + k] : pose[3 * k + j]);
-                T1[4 * i + j] = v;
-            }
-    }
-    float p1[12];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) p1[3 * r + c] = (float)T1[4 * r + c];
-        p1[9 + r] = (float)T1[4 * r + 3];
-    }
-    for (int k = 0; k < 12; k++)
-        if (!(fabsf(p1[k]) <= 3.4028234e38f)) return;  // (false for a NaN)
-    const float step = (float)step_size(p1, pose, la);
-    if (la.off || !(step > 0.f) || !(step <= 3.4028234e38f)) return;
-    const float beta = fminf(kPilotAlpha, kPilotCap / step);
-    float Tc[12];
-    for (int k = 0; k < 12; k++) {
-        Tc[k] = __fmaf_rn(beta, p1[k] - pose[k], pose[k]);
-        if (!(fabsf(Tc[k]) <= 3.4028234e38f)) return;
-    }
-    pose[kPoseBeta] = beta;
-    pose[kPoseOff] = beta * step;
-    for (int k = 0; k < 12; k++) pose[kPoseC + k] = hist[k] = Tc[k];
-}
-
-
-// One thread: solve the 3x3 problem of acc, T <- dT * T (device pose), stats as in pcp.h
-// (the host loop of pcp_icp_run, minus the convergence test).  A failed solve latches
-// stats[0] = -1 and freezes T.
-__global__ void k_icp_solve_dev(const double* acc, int do_scale, double* T, double* stats) {
-    if (stats[0] < 0) return;
-    double a[24], dT[16], Tn[16];
-    for (int k = 0; k < 24; k++) a[k] = acc[k];
-    stats[2] += a[23];
-    if (icp_solve(a, do_scale, dT) != PCP_OK) {
-        stats[0] = -1.0;
-        return;
-    }
-    stats[1] = sqrt(a[22] / a[0]);
-    stats[3] += 1.0;
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            double v = 0;
-            for (int k = 0; k < 4; k++) v += dT[4 * i + k] * T[4 * k + j];
-            Tn[4 * i + j] = v;
-        }
-    for (int k = 0; k < 16; k++) T[k] = Tn[k];
-}
-
-// The five kernels of a dense-grid launch after the first, on `st` (the context's stream, or a
-// stream under graph capture): verify what the candidate caches can settle, concatenate the
-// per-wave search segments, octant search of that list (`oct`), concatenate the fallback segments,
-// exact fallback.  `a` carries oct_g and ring_g; its partials end at the fallback pass's.
-using OctKernel = void (*)(IcpArgs, const int32_t*, const uint32_t*);
-// the dense first launch in its look-ahead form (after a pilot step): waves per SIMD and its grid
-// (6 waves/SIMD: 80 VGPRs and 144 B of scratch against 128 VGPRs and none at 4, but measured 0.11 ms
-// faster on the 50M first launch; the list launches of the same form stay at 4)
-#ifndef PCP_OCT_WAVES_LOOK0
-#define PCP_OCT_WAVES_LOOK0 6
-#endif
-int nb_look0(const pcp_icp* icp) { return PCP_OCT_WAVES_LOOK0 < PCP_OCT_WAVES ? icp->nb_fast_l : icp->nb_fast; }
-int icp_chain(pcp_icp* icp, hipStream_t st, IcpArgs& a, OctKernel oct) {
-    pcp_ctx* ctx = icp->ctx;
-    uint32_t* const svc_n = icp->sv_off + a.nseg_v;  // the two lists' lengths follow their segments' offsets
-    uint32_t* const fbc_n = icp->fb_off + a.nseg;
-    a.partials = icp->partials;
-    hipLaunchKernelGGL(k_icp_verify, dim3(icp->nb_ver), dim3(kIcpBlock), 0, st, a);
-    hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg_v + 3) / 4)), dim3(256), 0, st,
-                       (const int32_t*)icp->sv, (const uint32_t*)icp->sv_count, a.nseg_v, a.sv_seg, icp->svc, svc_n);
-    if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_ver, st));
-    a.partials += (int64_t)icp->nb_ver * kAcc;
-    hipLaunchKernelGGL(oct, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, st, a, (const int32_t*)icp->svc,
-                       (const uint32_t*)svc_n);
-    if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_mid, st));
-    hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg + 3) / 4)), dim3(256), 0, st,
-                       (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, a.nseg, a.fb_seg, icp->fbc, fbc_n);
-    a.partials += (int64_t)icp->nb_fast * kAcc;
-    hipLaunchKernelGGL(k_icp_ring, dim3(icp->nb_ring), dim3(kIcpBlock), 0, st, a, a.partials,
-                       (const int32_t*)icp->fbc, (const uint32_t*)fbc_n);
-    return PCP_OK;
-}
-
-// T (host) or T_dev (device pose, read by k_pose_from_T) -- exactly one is non-null
-int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, int32_t* corr_idx,
-               float* corr_d2, const double* T_dev = nullptr, IcpArgs* args_out = nullptr, bool pilot_ok = true) {
-    pcp_ctx* ctx = icp->ctx;
+// What the kernels read that is the same at every launch of the handle with this rmax: the target,
+// the queries, the caches, the lists and the search constants.  A launch adds dbg, oct_g, its
+// partials, when_beta and pilot_stride; R, t and launch are the kernels' own (load_pose).
+IcpArgs icp_args(const pcp_icp* icp, float rmax) {
     const pcp_index* tg = icp->target;
     IcpArgs a{};
     a.g = tg->g;
@@ -1874,23 +1325,7 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     a.q = icp->q;
     a.qidx = icp->qidx;
     a.nq = icp->nq;
-    a.nchunks = (icp->nq + kIcpBlock - 1) / kIcpBlock;
-    const Pose32 hp = T_dev ? Pose32{} : pose32(T);
-    LookAhead la{};
-    for (int k = 0; k < 3; k++) {
-        la.lo[k] = (float)(a.g.o[k] - rmax);
-        la.hi[k] = (float)(a.g.o[k] + a.g.n[k] * a.g.h + rmax);
-    }
-    la.alpha = kLookAlpha;
-    la.cap = kLookCap;
-    la.off = icp->no_look ? 1 : 0;
-    hipLaunchKernelGGL(k_pose_set, dim3(1), dim3(1), 0, ctx->stream, T_dev, hp, la, icp->pose_dev,
-                       icp->pose_hist + (icp->launches & (icp->narrow ? 63 : kHist - 1)) * 12,
-                       (uint32_t)icp->launches);
-    a.pose = icp->pose_dev;  // every kernel reads the pose (and the previous one) from HBM
-    a.launch_dev = (const uint32_t*)(icp->pose_dev + 24);  // ... and the launch index
-    for (int k = 0; k < 9; k++) a.R[k] = hp.R[k];
-    for (int k = 0; k < 3; k++) a.t[k] = hp.t[k];
+    a.pose = icp->pose_dev;  // every kernel reads the pose and the launch index from HBM
     a.r2 = rmax * rmax;
     a.mc = search_margin(a.g);  // >> fp32 rounding of the cell coordinates
     a.rho = 0.5f;
@@ -1904,7 +1339,6 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     a.dunit = (float)(a.g.h / 1024.0);
     a.inv_dunit = (float)(1024.0 / a.g.h);
     a.pose_hist = icp->pose_hist;
-    a.launch = (uint32_t)icp->launches;
     a.ntp = (uint32_t)tg->n;
     a.sv = icp->sv;
     a.sv_count = icp->sv_count;
@@ -1918,19 +1352,90 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     a.nb_fast = icp->nb_fast;
     a.nseg = (int64_t)icp->nb_fast * (kIcpBlock / 64);
     a.ring_all = a.g.dense ? 0 : 1;
-    a.dbg = icp->dbg;
-    double* part_v = icp->partials;
-    double* part_o = part_v + (int64_t)icp->nb_ver * kAcc;
-    double* part_r = part_o + (int64_t)icp->nb_fast * kAcc;
+    a.ring_g = icp->ring_g;
+    return a;
+}
+
+// One correspondence launch under the pose T (a host 4x4) or T_dev (a device one): exactly one is
+// non-null.
+struct LaunchReq {
+    const double* T = nullptr;
+    const double* T_dev = nullptr;
+    float rmax = 0.f;
+    double* acc_dev = nullptr;     // the launch's 24 sums
+    int32_t* corr_idx = nullptr;   // optional: the correspondences in caller order ...
+    float* corr_d2 = nullptr;      // ... and their d2
+    IcpArgs* keys_args = nullptr;  // the keys path: correspondences only -- nothing is accumulated, no pilot
+                                   // step (what is built on the keys minimises something else), no graph;
+                                   // receives the launch's arguments for k_make_keys
+    static LaunchReq host(const double* T, float rmax, double* acc) { return {T, nullptr, rmax, acc}; }
+    static LaunchReq dev(const double* T_dev, float rmax, double* acc) { return {nullptr, T_dev, rmax, acc}; }
+};
+
+using OctKernel = void (*)(IcpArgs, const int32_t*, const uint32_t*);
+// the dense first launch in its look-ahead form (after a pilot step): waves per SIMD and its grid
+// (6 waves/SIMD: 80 VGPRs and 144 B of scratch against 128 VGPRs and none at 4, but measured 0.11 ms
+// faster on the 50M first launch; the list launches of the same form stay at 4)
+#ifndef PCP_OCT_WAVES_LOOK0
+#define PCP_OCT_WAVES_LOOK0 6
+#endif
+int nb_look0(const pcp_icp* icp) { return PCP_OCT_WAVES_LOOK0 < PCP_OCT_WAVES ? icp->nb_fast_l : icp->nb_fast; }
+
+// The tail of every launch, on `st`: concatenate the octant pass's per-wave fallback segments into
+// one list, then the exact fallback pass over it (a sparse grid has no octant pass and no list: the
+// fallback pass takes every query).  Its partials are the last of the launch.
+void icp_fallback(pcp_icp* icp, hipStream_t st, IcpArgs& a) {
+    uint32_t* const fbc_n = icp->fb_off + a.nseg;  // the list's length follows its segments' offsets
+    if (a.g.dense)
+        hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg + 3) / 4)), dim3(256), 0, st,
+                           (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, a.nseg, a.fb_seg, icp->fbc, fbc_n);
+    a.partials = icp->partials + (int64_t)(icp->nb_ver + icp->nb_fast) * kAcc;
+    hipLaunchKernelGGL(k_icp_ring, dim3(icp->nb_ring), dim3(kIcpBlock), 0, st, a, a.partials,
+                       (const int32_t*)icp->fbc, (const uint32_t*)fbc_n);
+}
+
+// The five kernels of a dense-grid launch after the first, on `st` (the context's stream, or a
+// stream under graph capture): verify what the candidate caches can settle, concatenate the
+// per-wave search segments, octant search of that list (`oct`), then icp_fallback.  `a` carries
+// oct_g.
+int icp_chain(pcp_icp* icp, hipStream_t st, IcpArgs& a, OctKernel oct) {
+    pcp_ctx* ctx = icp->ctx;
+    uint32_t* const svc_n = icp->sv_off + a.nseg_v;  // the search list's length, as the fallback list's
+    a.partials = icp->partials;
+    hipLaunchKernelGGL(k_icp_verify, dim3(icp->nb_ver), dim3(kIcpBlock), 0, st, a);
+    hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg_v + 3) / 4)), dim3(256), 0, st,
+                       (const int32_t*)icp->sv, (const uint32_t*)icp->sv_count, a.nseg_v, a.sv_seg, icp->svc, svc_n);
+    if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_ver, st));
+    a.partials += (int64_t)icp->nb_ver * kAcc;
+    hipLaunchKernelGGL(oct, dim3(icp->nb_fast_l), dim3(kIcpBlock), 0, st, a, (const int32_t*)icp->svc,
+                       (const uint32_t*)svc_n);
+    if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_mid, st));
+    icp_fallback(icp, st, a);
+    return PCP_OK;
+}
+
+int icp_launch(pcp_icp* icp, const LaunchReq& rq) {
+    pcp_ctx* ctx = icp->ctx;
+    const bool keys = rq.keys_args != nullptr;
+    IcpArgs a = icp_args(icp, rq.rmax);
+    a.dbg = icp->dbg | (keys ? kDbgNoAccum : 0);
+    LookAhead la{};
+    for (int k = 0; k < 3; k++) {
+        la.lo[k] = (float)(a.g.o[k] - rq.rmax);
+        la.hi[k] = (float)(a.g.o[k] + a.g.n[k] * a.g.h + rq.rmax);
+    }
+    la.alpha = kLookAlpha;
+    la.cap = kLookCap;
+    la.off = icp->no_look ? 1 : 0;
+    hipLaunchKernelGGL(k_pose_set, dim3(1), dim3(1), 0, ctx->stream, rq.T_dev, rq.T_dev ? Pose32{} : pose32(rq.T), la,
+                       icp->pose_dev, icp->pose_hist + (icp->launches & (icp->narrow ? 63 : kHist - 1)) * 12,
+                       (uint32_t)icp->launches);
     hipEvent_t e0 = icp->ev0, e1 = icp->ev1;
-    if (T_dev) {  // device-resident loop: one event pair per launch, read by pcp_icp_kernel_ms
+    if (rq.T_dev) {  // device-resident loop: one event pair per launch, read by pcp_icp_kernel_ms
         if (icp->ntev == icp->tev.size()) {
             std::pair<hipEvent_t, hipEvent_t> pr{nullptr, nullptr};
-            PCP_HIP(ctx, pcp::event_get(ctx, &pr.first));
-            if (pcp::event_get(ctx, &pr.second) != hipSuccess) {
-                pcp::event_put(ctx, pr.first);
-                return set_error(ctx, PCP_ERR_HIP, "hipEventCreate");
-            }
+            PCP_HIP(ctx, icp->mem.event(&pr.first));
+            PCP_HIP(ctx, icp->mem.event(&pr.second));
             icp->tev.push_back(pr);
         }
         e0 = icp->tev[icp->ntev].first;
@@ -1951,18 +1456,16 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     const OctKernel oct_list = icp->launches <= 1 ? k_icp_octant<PCP_OCT_WAVES_LIST, false> : oct_graph;
     if (verify) {
         a.oct_g = icp->oct_g_list;
-        a.ring_g = icp->ring_g;
         // A device-pose launch after the first is the same five kernels every time with the same
         // arguments: the launch index is read from the device (k_pose_set) and the pose was already.
         // With PCP_ICP_OPT_GRAPH the chain is captured once per handle into a HIP graph and replayed --
         // one launch instead of five (measured: host enqueue is not what the loop waits for, and the
         // replayed chain ran 0.5 % slower, so it is off by default).
-        const bool graph = icp->graph && T_dev && !icp->dbg && !corr_idx && !args_out && !icp->graph_off &&
+        const bool graph = icp->graph && rq.T_dev && !icp->dbg && !rq.corr_idx && !keys && !icp->graph_off &&
                            oct_list == oct_graph;
-        if (graph && icp->gexec && icp->graph_r2 != a.r2) {  // captured for another rmax (replays are stream-ordered)
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipGraphExecDestroy(icp->gexec);
-            icp->gexec = nullptr;
+        if (graph && icp->gexec && icp->graph_r2 != a.r2) {  // captured for another rmax
+            icp_graph_drop(icp);                              // (it selects the owner's device)
+            PCP_HIP(ctx, hipSetDevice(ctx->device));
         }
         if (graph && !icp->gexec) {  // captured on the context's side stream (capture enqueues nothing)
             hipStream_t cap = nullptr;
@@ -1987,8 +1490,9 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
     } else {
         // the first launch (nothing cached: the octant search takes every query) or a sparse grid
         // (the fallback pass takes every query)
+        double* const part_o = icp->partials + (int64_t)icp->nb_ver * kAcc;
         const int nb_idle = a.g.dense ? icp->nb_ver : icp->nb_ver + icp->nb_fast;
-        PCP_HIP(ctx, hipMemsetAsync(part_v, 0, (size_t)nb_idle * kAcc * sizeof(double), ctx->stream));
+        PCP_HIP(ctx, hipMemsetAsync(icp->partials, 0, (size_t)nb_idle * kAcc * sizeof(double), ctx->stream));
         if (a.g.dense) {
             if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_ver, ctx->stream));
             a.partials = part_o;
@@ -1998,7 +1502,7 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
             // of the queries (the pilot) -- gives beta_0 and T_c (k_pilot_map).  beta_0 is known on
             // the device only, so both forms of the search are enqueued and the one it did not
             // choose exits at once: beta_0 = 0 runs exactly the plain first launch.
-            const bool pilot = pilot_ok && !icp->has_pred && !icp->no_pilot && !icp->dbg && icp->nq > 0 &&
+            const bool pilot = !keys && !icp->has_pred && !icp->no_pilot && !icp->dbg && icp->nq > 0 &&
                                (icp->pilot_always || icp->nq >= kPilotMinQueries);
             const bool look0 = icp->launches == 0 && !icp->no_look && (icp->has_pred || pilot);
             if (look0) {
@@ -2027,416 +1531,39 @@ int icp_launch(pcp_icp* icp, const double T[16], float rmax, double* acc_dev, in
             a.when_beta = 0;
         }
         if (icp->dbg) PCP_HIP(ctx, hipEventRecord(icp->ev_mid, ctx->stream));
-        if (a.g.dense) {  // compact the per-wave fallback segments into one list
-            hipLaunchKernelGGL(k_list_compact, dim3((unsigned)((a.nseg + 3) / 4)), dim3(256), 0, ctx->stream,
-                               (const int32_t*)icp->fb, (const uint32_t*)icp->fb_count, a.nseg, a.fb_seg, icp->fbc,
-                               icp->fb_off + a.nseg);
-        }
-        a.partials = part_r;
-        a.ring_g = icp->ring_g;
-        hipLaunchKernelGGL(k_icp_ring, dim3(icp->nb_ring), dim3(kIcpBlock), 0, ctx->stream, a, part_r,
-                           (const int32_t*)icp->fbc, (const uint32_t*)(icp->fb_off + a.nseg));
+        icp_fallback(icp, ctx->stream, a);
     }
     PCP_HIP(ctx, hipEventRecord(e1, ctx->stream));
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kAcc * kRedGroups), 0, ctx->stream, icp->partials,
-                       icp->nb_ver + icp->nb_fast + icp->nb_ring, acc_dev,
+                       icp->nb_ver + icp->nb_fast + icp->nb_ring, rq.acc_dev,
                        a.g.dense ? (const uint32_t*)(icp->fb_off + a.nseg) : nullptr);
-    if (corr_idx) {
+    if (rq.corr_idx) {
         if (icp->nq_in > icp->nq)  // non-finite queries were dropped at create time
-            hipLaunchKernelGGL(k_fill_corr, dim3(grid_for(icp->nq_in, 256)), dim3(256), 0, ctx->stream, corr_idx,
-                               corr_d2, icp->nq_in);
+            hipLaunchKernelGGL(k_fill_corr, dim3(grid_for(icp->nq_in, 256)), dim3(256), 0, ctx->stream, rq.corr_idx,
+                               rq.corr_d2, icp->nq_in);
         if (icp->nq > 0)
             hipLaunchKernelGGL(k_scatter_corr, dim3(grid_for(icp->nq, 256)), dim3(256), 0, ctx->stream, a,
-                               corr_idx, corr_d2);
+                               rq.corr_idx, rq.corr_d2);
     }
-    if (args_out) *args_out = a;
+    if (keys) *rq.keys_args = a;
     icp->launches++;
     PCP_LAUNCH_CHECK(ctx);
     return PCP_OK;
 }
 
-// S = acc[7..15] - n qm pm^T cancels down from `scale` = max(|acc[7..15]|, n |qm| |pm|): each entry
-// carries a few eps * scale of rounding, so a largest singular value within kRank0 eps * scale is
-// noise, not a direction (every pair at one target point, or every query at one point).
-constexpr double kRank0 = 64.0, kEps = 2.220446049250313e-16;
-
-__host__ __device__ int icp_solve(const double acc[24], int do_scale, double dT[16]) {
-    const double n = acc[0];
-    if (!(n >= 3.0)) return PCP_ERR_ICP;
-    for (int k = 0; k < 23; k++)  // a NaN or an infinity among the sums (false for a NaN)
-        if (!(fabs(acc[k]) <= 1.7976931348623157e308)) return PCP_ERR_ICP;
-    double qm[3], pm[3], S[9];
-    for (int k = 0; k < 3; k++) { qm[k] = acc[1 + k] / n; pm[k] = acc[4 + k] / n; }
-    // S = sum (q - qm)(p - pm)^T ; optimal R maximises trace(R S): S = U s V^T, R = V D U^T
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) S[3 * a + b] = acc[7 + 3 * a + b] - n * qm[a] * pm[b];
-    double U[9], s[3], V[9];
-    svd3(S, U, s, V);
-    double scale = n * sqrt((qm[0] * qm[0] + qm[1] * qm[1] + qm[2] * qm[2]) *
-                            (pm[0] * pm[0] + pm[1] * pm[1] + pm[2] * pm[2]));
-    for (int k = 7; k < 16; k++) scale = fmax(scale, fabs(acc[k]));
-    // rank 0: no rotation is preferred, so none is made (the pairs' centroids still align)
-    const bool rank0 = !(s[0] > kRank0 * kEps * scale);
-    double R[9];
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            double v = 0;
-            for (int k = 0; k < 3; k++) v += V[3 * a + k] * U[3 * b + k];
-            R[3 * a + b] = rank0 ? (a == b ? 1.0 : 0.0) : v;
-        }
-    double d = det3(R) < 0 ? -1.0 : 1.0;
-    if (d < 0) {  // flip the axis of the smallest singular value
-        for (int a = 0; a < 3; a++)
-            for (int b = 0; b < 3; b++) R[3 * a + b] -= 2.0 * V[3 * a + 2] * U[3 * b + 2];
-    }
-    double sc = 1.0;
-    if (do_scale && !rank0) {
-        const double var = (acc[16] + acc[19] + acc[21]) - n * (qm[0] * qm[0] + qm[1] * qm[1] + qm[2] * qm[2]);
-        if (var > 0) sc = (s[0] + s[1] + d * s[2]) / var;
-    }
-    for (int a = 0; a < 3; a++) {
-        double t = pm[a];
-        for (int b = 0; b < 3; b++) {
-            dT[4 * a + b] = sc * R[3 * a + b];
-            t -= sc * R[3 * a + b] * qm[b];
-        }
-        dT[4 * a + 3] = t;
-    }
-    dT[12] = dT[13] = dT[14] = 0.0;
-    dT[15] = 1.0;
-    return PCP_OK;
-}
-
 }  // namespace pcp
 
 extern "C" {
-
-int pcp_icp_check_sizes(int64_t n_target, int64_t nq) {
-    if (n_target < 0 || nq < 0) return PCP_ERR_ARG;
-    if (nq >= ((int64_t)1 << 31)) return PCP_ERR_ARG;
-    // ld16(): 32-bit byte offsets into the fp32 target (n_target records + the far sentinel)
-    if (n_target + 1 >= ((int64_t)1 << 28)) return PCP_ERR_CAPACITY;
-    return PCP_OK;
-}
-
-}  // extern "C"
-
-namespace pcp {
-namespace {
-
-// the query sort of an ICP handle between its launch and its completion: keys of the octant-block
-// bricks of the target grid, a stable radix sort with the 16-byte records as payload, the count
-// of finite queries
-struct QuerySort {
-    Tmp blocks;
-    uint32_t *k0 = nullptr, *k1 = nullptr;
-    float4 *r0 = nullptr, *qs = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    char* tmp = nullptr;
-    hipEvent_t done = nullptr;
-    int64_t nq = 0;
-    explicit QuerySort(pcp_ctx* ctx) : blocks(ctx) {}
-    // The blocks go back to the cache in ctx->stream's order, so only once that stream has waited
-    // for `done` (or the side stream was synchronised after a failure): every path of the two
-    // create functions calls this there, and none leaves the blocks to the guard's scope exit.
-    void release() {
-        blocks.free_all();
-        if (done) event_put(blocks.ctx, done);
-        done = nullptr;
-    }
-};
-
-int icp_check_grid(pcp_ctx* ctx, const GridDesc& g, int64_t n_target, int64_t nq) {
-    if (int rc = pcp_icp_check_sizes(n_target, nq))
-        return set_error(ctx, rc, rc == PCP_ERR_CAPACITY ? "ICP target must have < 2^28 - 1 points (32-bit record offsets)"
-                                                         : "ICP supports < 2^31 queries");
-    if (g.nbricks * 64 >= ((int64_t)1 << 32) ||
-        qbricks(g, 0) * qbricks(g, 1) * qbricks(g, 2) * kQBrick * kQBrick * kQBrick >= ((int64_t)1 << 32))
-        return set_error(ctx, PCP_ERR_UNSUPPORTED, "ICP target grid too large for 32-bit cell keys");
-    return PCP_OK;
-}
-
-// enqueue the query sort on `st` (after everything enqueued so far on ctx->stream); `s.done` is
-// recorded on `st` when it is complete
-int qsort_launch(pcp_ctx* ctx, hipStream_t st, const GridDesc& g, const float* q, size_t q_stride, int64_t nq,
-                 QuerySort& s) {
-    s.nq = nq;
-    PCP_TRY(s.blocks.get(&s.k0, nq));
-    PCP_TRY(s.blocks.get(&s.k1, nq));
-    PCP_TRY(s.blocks.get(&s.r0, nq));
-    PCP_TRY(s.blocks.get(&s.qs, nq + 1));
-    PCP_TRY(s.blocks.get(&s.d_cnt, 1));
-    PCP_HIP(ctx, event_get(ctx, &s.done));
-    unsigned bits = 1;  // keys are in [0, query_key_end]
-    while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)query_key_end(g)) bits++;
-    size_t tb = 0;
-    if (nq > 0) {
-        PCP_HIP(ctx, rocprim::radix_sort_pairs<RecSortConfig>(nullptr, tb, s.k0, s.k1, s.r0, s.qs, (size_t)nq, 0u, bits, st));
-        PCP_TRY(s.blocks.get(&s.tmp, tb));
-    }
-    // Every block the side stream uses is allocated above, before `go` is recorded: a block the
-    // context cache hands out after that point could still be in use by main-stream work the side
-    // stream does not wait for.
-    if (st != ctx->stream) {  // the side stream starts after the main stream's work so far
-        hipEvent_t go = nullptr;
-        PCP_HIP(ctx, event_get(ctx, &go));
-        hipError_t e = hipEventRecord(go, ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, go, 0);
-        event_put(ctx, go);  // (reused only by a later record on ctx->stream: stream-ordered)
-        if (e != hipSuccess) return hip_fail(ctx, e, "query sort stream order", __FILE__, __LINE__);
-    }
-    PCP_HIP(ctx, hipMemsetAsync(s.d_cnt, 0, sizeof(unsigned long long), st));
-    if (nq > 0) {
-        hipLaunchKernelGGL(k_query_keys, dim3(grid_for(nq, 256)), dim3(256), 0, st, g, q, q_stride / sizeof(float), nq,
-                           s.k0, s.r0);
-        PCP_HIP(ctx, rocprim::radix_sort_pairs<RecSortConfig>(s.tmp, tb, s.k0, s.k1, s.r0, s.qs, (size_t)nq, 0u, bits, st));
-        hipLaunchKernelGGL(k_first_at_least, dim3(1), dim3(1), 0, st, s.k1, nq, query_key_end(g), s.d_cnt);
-    }
-    PCP_HIP(ctx, hipGetLastError());
-    PCP_HIP(ctx, hipEventRecord(s.done, st));
-    return PCP_OK;
-}
-
-// the sorted records -> 12-byte xyz + original indices, on ctx->stream after the sort
-int qsort_finish(pcp_ctx* ctx, Tmp& tmp, QuerySort& s, QXyz** q3, int32_t** qi, int64_t* nfin) {
-    PCP_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.done, 0));
-    unsigned long long hc = 0;
-    PCP_HIP(ctx, hipMemcpyAsync(&hc, s.d_cnt, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream));
-    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *nfin = (int64_t)hc;
-    PCP_TRY(tmp.get(q3, s.nq + 1));
-    PCP_TRY(tmp.get(qi, s.nq + 1));
-    if (*nfin > 0)
-        hipLaunchKernelGGL(k_split_queries, dim3(grid_for(*nfin, 256)), dim3(256), 0, ctx->stream,
-                           (const float4*)s.qs, *nfin, *q3, *qi);
-    PCP_HIP(ctx, hipGetLastError());
-    return PCP_OK;
-}
-
-// the handle over sorted queries (q3, qi: owned by the handle from here on)
-int icp_make(pcp_ctx* ctx, const pcp_index* target, QXyz* q3, int32_t* qi, int64_t nfin, int64_t nq, pcp_icp** out) {
-    pcp_icp* icp = new pcp_icp();
-    icp->ctx = ctx;
-    icp->owner = ctx;
-    ctx_retain(ctx);
-    icp->target = target;
-    icp->nq = nfin;
-    icp->nq_in = nq;
-    icp->q = q3;
-    icp->qidx = qi;
-    int dev_cus = 256;  // one attribute query (the whole hipDeviceProp_t costs ~0.1 ms per create)
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0)
-        dev_cus = cus;
-    const int64_t want = (icp->nq + kIcpBlock - 1) / kIcpBlock;
-    icp->nb_fast = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)dev_cus * PCP_OCT_WAVES));
-    icp->nb_fast_l = (int)std::max<int64_t>(1, std::min<int64_t>(icp->nb_fast, (int64_t)dev_cus * PCP_OCT_WAVES_LIST));
-    icp->nb_ring = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)dev_cus * PCP_RING_WAVES));
-    const int64_t nwaves = (int64_t)icp->nb_fast * (kIcpBlock / 64);
-    const int64_t nwaves_l = (int64_t)icp->nb_fast_l * (kIcpBlock / 64);  // the smaller grid: larger segments
-    const int64_t nchunks64 = (icp->nq + 63) / 64;
-    icp->fb_seg = ((nchunks64 + nwaves_l - 1) / nwaves_l) * 64;
-    icp->nb_ver = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)dev_cus * PCP_VER_WAVES));
-    const int64_t nwaves_v = (int64_t)icp->nb_ver * (kIcpBlock / 64);
-    icp->sv_seg = ((nchunks64 + nwaves_v - 1) / nwaves_v) * 64;  // contiguous ranges: <= this per wave
-    icp->nseg_v = nwaves_v;
-    int rc = dmalloc(ctx, &icp->partials, (size_t)(icp->nb_ver + icp->nb_fast + icp->nb_ring) * kAcc);
-    if (!rc) rc = dmalloc(ctx, &icp->acc, kAcc);
-    if (!rc) rc = dmalloc(ctx, &icp->pilot_acc, kAcc);
-    // 24 pose floats, the launch index, the look-ahead state and map (kPoseStep .. kPoseWords)
-    if (!rc) rc = dmalloc(ctx, &icp->pose_dev, kPoseWords);
-    // 12-byte cache records when every position (and the far sentinel) fits 26 bits
-    icp->narrow = target->n + 1 < (int64_t)kPos26;
-    const int rw = icp->narrow ? 3 : 4;  // words per record
-    if (!rc) rc = dmalloc(ctx, &icp->cand, (size_t)(icp->nq + 1) * rw);
-    if (!rc) rc = dmalloc(ctx, &icp->pose_hist, kHist * 12);
-    // the first launch over a dense grid (the octant pass over every query) writes every cache
-    // record before any pass reads one: only the sentinel record needs its value then (an 800 MB
-    // memset at 50M queries, ~0.1 ms of the pre-iteration span, otherwise).  An empty record has
-    // no positions and D = 0 (wide: NaN), so it is never settled from.
-    const bool cand_all = !target->g.dense;
-    const int64_t r0 = cand_all ? 0 : icp->nq, nr = cand_all ? icp->nq + 1 : 1;
-    hipError_t me = hipSuccess;
-    if (!rc)
-        me = icp->narrow ? hipMemsetD32Async((hipDeviceptr_t)(icp->cand + r0 * rw), (int)kPos26, (size_t)(nr * rw),
-                                             ctx->stream)
-                         : hipMemsetAsync(icp->cand + r0 * rw, 0xff, (size_t)nr * 16, ctx->stream);
-    if (!rc && (me != hipSuccess ||
-                hipMemsetAsync(icp->pose_hist, 0, kHist * 12 * sizeof(float), ctx->stream) != hipSuccess ||
-                hipMemsetAsync(icp->pose_dev, 0, kPoseWords * sizeof(float), ctx->stream) != hipSuccess))
-        rc = set_error(ctx, PCP_ERR_HIP, "memset");
-    if (!rc) rc = dmalloc(ctx, &icp->sv, (size_t)icp->nseg_v * icp->sv_seg + 1);
-    if (!rc) rc = dmalloc(ctx, &icp->sv_count, (size_t)icp->nseg_v);
-    if (!rc) rc = dmalloc(ctx, &icp->sv_off, (size_t)icp->nseg_v + 1);
-    if (!rc) rc = dmalloc(ctx, &icp->svc, icp->nq + 1);
-    const int64_t fb_cap = std::max<int64_t>(nwaves * icp->fb_seg, icp->nq);
-    if (!rc) rc = dmalloc(ctx, &icp->fb, (size_t)fb_cap + 1);
-    if (!rc) rc = dmalloc(ctx, &icp->fb_count, (size_t)nwaves);
-    if (!rc) rc = dmalloc(ctx, &icp->fb_off, (size_t)nwaves + 1);
-    if (!rc) rc = dmalloc(ctx, &icp->fbc, icp->nq + 1);
-    if (!rc && (event_get(ctx, &icp->ev0) != hipSuccess || event_get(ctx, &icp->ev1) != hipSuccess ||
-                event_get(ctx, &icp->ev_mid) != hipSuccess || event_get(ctx, &icp->ev_ver) != hipSuccess))
-        rc = set_error(ctx, PCP_ERR_HIP, "hipEventCreate failed");
-    if (rc) {
-        pcp_icp_destroy(icp);
-        return rc;
-    }
-    *out = icp;
-    return PCP_OK;
-}
-
-}  // namespace
-
-// common.hpp: the handle's facts the point-to-plane loop (icp_plane.hip) checks its arguments by
-const pcp_index* icp_target(const pcp_icp* icp) { return icp->target; }
-int64_t icp_query_count(const pcp_icp* icp) { return icp->nq_in; }
-
-}  // namespace pcp
-
-extern "C" {
-
-int pcp_icp_create(pcp_ctx* ctx, const pcp_index* target, const float* q, size_t q_stride, int64_t nq,
-                   pcp_icp** out) {
-    if (!ctx || !target || !out || nq < 0 || (nq > 0 && !q)) return PCP_ERR_ARG;
-    if (target->is_f64) return pcp::set_error(ctx, PCP_ERR_ARG, "ICP target must be an fp32 index");
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    *out = nullptr;
-    if (q_stride == 0) q_stride = 3 * sizeof(float);
-    if (q_stride % sizeof(float)) return pcp::set_error(ctx, PCP_ERR_ARG, "query stride must be whole floats");
-    PCP_TRY(pcp::icp_check_grid(ctx, target->g, target->n, nq));
-    pcp::Tmp tmp(ctx);  // q3, qi until the handle owns them
-    pcp::QuerySort s(ctx);
-    pcp::QXyz* q3 = nullptr;
-    int32_t* qi = nullptr;
-    int64_t nfin = 0;
-    int rc = pcp::qsort_launch(ctx, ctx->stream, target->g, q, q_stride, nq, s);
-    if (!rc) rc = pcp::qsort_finish(ctx, tmp, s, &q3, &qi, &nfin);
-    s.release();  // early: the handle's buffers are served from these blocks
-    if (rc) return rc;
-    return pcp::icp_make(ctx, target, tmp.release(q3), tmp.release(qi), nfin, nq, out);
-}
-
-int pcp_icp_create_with_target(pcp_ctx* ctx, const float* target_xyz, size_t t_stride, int64_t n_target,
-                               double cell_size, const float* q, size_t q_stride, int64_t nq, pcp_index** index_out,
-                               pcp_icp** icp_out) {
-    if (!ctx || !index_out || !icp_out || nq < 0 || (nq > 0 && !q) || n_target < 0 || (n_target > 0 && !target_xyz))
-        return PCP_ERR_ARG;
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    *index_out = nullptr;
-    *icp_out = nullptr;
-    if (q_stride == 0) q_stride = 3 * sizeof(float);
-    if (q_stride % sizeof(float)) return pcp::set_error(ctx, PCP_ERR_ARG, "query stride must be whole floats");
-    // the query sort needs only the target grid's geometry: it runs on the side stream while the
-    // target's cell sort runs on the main stream (two independent radix sorts overlapped)
-    pcp::Tmp tmp(ctx);  // q3, qi until the handle owns them
-    pcp::QuerySort s(ctx);
-    bool launched = false;
-    const pcp::GeomHook hook = [&](const pcp::GridDesc& g) -> int {
-        PCP_TRY(pcp::icp_check_grid(ctx, g, n_target, nq));
-        hipStream_t side = nullptr;
-        PCP_TRY(pcp::side_stream(ctx, &side));
-        launched = true;
-        return pcp::qsort_launch(ctx, side, g, q, q_stride, nq, s);
-    };
-    pcp_index* ix = nullptr;
-    int rc = pcp::index_build_f32_hooked(ctx, target_xyz, t_stride, n_target, cell_size, &ix, hook);
-    pcp::QXyz* q3 = nullptr;
-    int32_t* qi = nullptr;
-    int64_t nfin = 0;
-    if (!rc && !launched) rc = pcp::qsort_launch(ctx, ctx->stream, ix->g, q, q_stride, nq, s);
-    if (!rc) rc = pcp::qsort_finish(ctx, tmp, s, &q3, &qi, &nfin);
-    if (rc && launched) (void)hipStreamSynchronize(ctx->side);  // the side stream's work is over
-    s.release();  // early: the handle's buffers are served from these blocks
-    if (!rc) rc = pcp::icp_make(ctx, ix, tmp.release(q3), tmp.release(qi), nfin, nq, icp_out);
-    if (rc) {
-        if (ix) pcp_index_destroy(ix);
-        return rc;
-    }
-    *index_out = ix;
-    return PCP_OK;
-}
-
-int pcp_icp_set_options(pcp_icp* icp, int oct_lanes_first, int oct_lanes_list, int ring_lanes, int ablate) {
-    if (!icp) return PCP_ERR_ARG;
-    auto lanes = [](int v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8; };
-    pcp_ctx* ctx = icp->owner;
-    // every check and allocation first: a failed call leaves the handle as it was
-    if (!lanes(oct_lanes_first) || !lanes(oct_lanes_list) || !lanes(ring_lanes) || ablate < 0)
-        return pcp::set_error(ctx, PCP_ERR_ARG, "pcp_icp_set_options: lanes must be 0, 1, 2, 4 or 8; ablate >= 0");
-    const bool widen = (ablate & PCP_ICP_OPT_WIDE_CACHE) && icp->narrow;
-    if (widen && icp->launches > 0)
-        return pcp::set_error(ctx, PCP_ERR_ARG, "PCP_ICP_OPT_WIDE_CACHE only before the handle's first launch");
-    if (widen) {  // re-create the records in the 16-byte form
-        pcp::Tmp tmp(ctx);
-        uint32_t* w = nullptr;
-        PCP_TRY(tmp.get(&w, (size_t)(icp->nq + 1) * 4));
-        if (hipMemsetAsync(w, 0xff, (size_t)(icp->nq + 1) * 16, ctx->stream) != hipSuccess)
-            return pcp::set_error(ctx, PCP_ERR_HIP, "pcp_icp_set_options: memset");
-        pcp::dfree(ctx, icp->cand);
-        icp->cand = tmp.release(w);
-        icp->narrow = false;
-    }
-    if (icp->gexec) {  // captured with the old lanes / flags
-        (void)hipStreamSynchronize(icp->ctx->stream);
-        (void)hipGraphExecDestroy(icp->gexec);
-        icp->gexec = nullptr;
-    }
-    icp->oct_g_first = oct_lanes_first ? oct_lanes_first : 1;
-    icp->oct_g_list = oct_lanes_list;
-    icp->ring_g = ring_lanes;
-    icp->dbg = ablate & ~(PCP_ICP_OPT_WIDE_CACHE | PCP_ICP_OPT_GRAPH | PCP_ICP_OPT_NO_LOOKAHEAD |
-                          PCP_ICP_OPT_NO_PILOT | PCP_ICP_OPT_PILOT_ALWAYS);
-    icp->graph = (ablate & PCP_ICP_OPT_GRAPH) != 0;
-    icp->no_look = (ablate & PCP_ICP_OPT_NO_LOOKAHEAD) != 0;
-    icp->no_pilot = (ablate & PCP_ICP_OPT_NO_PILOT) != 0;
-    icp->pilot_always = (ablate & PCP_ICP_OPT_PILOT_ALWAYS) != 0;
-    return PCP_OK;
-}
-
-int pcp_icp_destroy(pcp_icp* icp) {
-    if (!icp) return PCP_ERR_ARG;
-    (void)hipSetDevice(icp->owner->device);
-    if (icp->gexec) {  // (after its last replay has run)
-        (void)hipStreamSynchronize(icp->ctx->stream);
-        (void)hipGraphExecDestroy(icp->gexec);
-    }
-    pcp::dfree(icp->owner, icp->q);
-    pcp::dfree(icp->owner, icp->qidx);
-    pcp::dfree(icp->owner, icp->partials);
-    pcp::dfree(icp->owner, icp->acc);
-    pcp::dfree(icp->owner, icp->pilot_acc);
-    pcp::dfree(icp->owner, icp->cand);
-    pcp::dfree(icp->owner, icp->pose_hist);
-    pcp::dfree(icp->owner, icp->sv);
-    pcp::dfree(icp->owner, icp->sv_count);
-    pcp::dfree(icp->owner, icp->sv_off);
-    pcp::dfree(icp->owner, icp->svc);
-
-    pcp::dfree(icp->owner, icp->fb);
-    pcp::dfree(icp->owner, icp->fb_count);
-    pcp::dfree(icp->owner, icp->fb_off);
-    pcp::dfree(icp->owner, icp->fbc);
-    pcp::dfree(icp->owner, icp->pose_dev);
-    pcp::event_put(icp->owner, icp->ev0);
-    pcp::event_put(icp->owner, icp->ev1);
-    pcp::event_put(icp->owner, icp->ev_mid);
-    pcp::event_put(icp->owner, icp->ev_ver);
-    for (auto& pr : icp->tev) {
-        pcp::event_put(icp->owner, pr.first);
-        pcp::event_put(icp->owner, pr.second);
-    }
-    pcp_ctx* owner = icp->owner;
-    delete icp;
-    pcp::ctx_release(owner);
-    return PCP_OK;
-}
 
 int pcp_icp_step(pcp_ctx* ctx, pcp_icp* icp, const double T[16], float rmax, double* acc_dev,
                  int32_t* corr_idx, float* corr_d2) {
     if (!ctx || !icp || !T || !acc_dev || (corr_idx && !corr_d2) || !(rmax >= 0.f)) return PCP_ERR_ARG;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     icp->ctx = ctx;
-    PCP_TRY(pcp::icp_launch(icp, T, rmax, acc_dev, corr_idx, corr_d2));
+    pcp::LaunchReq rq = pcp::LaunchReq::host(T, rmax, acc_dev);
+    rq.corr_idx = corr_idx;
+    rq.corr_d2 = corr_d2;
+    PCP_TRY(pcp::icp_launch(icp, rq));
     double fbn = 0.0;
     PCP_HIP(ctx, hipMemcpyAsync(&fbn, acc_dev + 23, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     uint32_t nsv = (uint32_t)icp->nq;  // sparse grid / first launch: every query is searched
@@ -2469,13 +1596,10 @@ static int icp_keys(pcp_ctx* ctx, pcp_icp* icp, const double* T, const double* T
         return PCP_ERR_ARG;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     icp->ctx = ctx;
-    const int saved = icp->dbg;
-    icp->dbg |= pcp::kDbgNoAccum;  // correspondences only
     pcp::IcpArgs a{};
-    // (the loops built on the keys minimise something else: no pilot step for them)
-    const int rc = pcp::icp_launch(icp, T, rmax, icp->acc, nullptr, nullptr, T_dev, &a, false);
-    icp->dbg = saved;
-    PCP_TRY(rc);
+    pcp::LaunchReq rq = T_dev ? pcp::LaunchReq::dev(T_dev, rmax, icp->acc) : pcp::LaunchReq::host(T, rmax, icp->acc);
+    rq.keys_args = &a;  // correspondences only
+    PCP_TRY(pcp::icp_launch(icp, rq));
     if (icp->nq_in > icp->nq)
         hipLaunchKernelGGL(pcp::k_fill_keys, dim3(pcp::grid_for(icp->nq_in, 256)), dim3(256), 0, ctx->stream, keys_dev,
                            icp->nq_in);
@@ -2496,68 +1620,6 @@ int pcp_icp_keys_dev(pcp_ctx* ctx, pcp_icp* icp, const double* T_dev, float rmax
     return icp_keys(ctx, icp, nullptr, T_dev, rmax, target_offset, keys_dev);
 }
 
-int pcp_keys_owner(pcp_ctx* ctx, const uint64_t* keys_dev, int64_t n, const int64_t* bounds_dev, int nshards,
-                   uint8_t* owner_dev) {
-    if (!ctx || n < 0 || (n > 0 && (!keys_dev || !owner_dev)) || !bounds_dev || nshards < 1 || nshards > 255)
-        return PCP_ERR_ARG;
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    if (n == 0) return PCP_OK;
-    hipLaunchKernelGGL(pcp::k_keys_owner, dim3(pcp::grid_for(n, 256, 8192)), dim3(256), 0, ctx->stream, keys_dev, n,
-                       bounds_dev, nshards, owner_dev);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
-}
-
-int pcp_icp_accumulate_owned(pcp_ctx* ctx, const double* T_dev, const float* q_dev, size_t q_stride, int64_t nq,
-                             const uint64_t* keys_dev, const uint8_t* owner_dev, int rank, int64_t lo, int64_t hi,
-                             const float* shard_xyz_dev, size_t shard_stride, double* acc_dev) {
-    if (!ctx || !T_dev || nq < 0 || (nq > 0 && (!q_dev || !keys_dev || !owner_dev)) || !acc_dev || rank < 0 ||
-        rank > 254 || lo < 0 || hi < lo || (hi > lo && !shard_xyz_dev))
-        return PCP_ERR_ARG;
-    if (q_stride == 0) q_stride = 3 * sizeof(float);
-    if (shard_stride == 0) shard_stride = 3 * sizeof(float);
-    if (q_stride % sizeof(float) || shard_stride % sizeof(float))
-        return pcp::set_error(ctx, PCP_ERR_ARG, "strides must be whole floats");
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    const int nb = (int)std::min<int64_t>(std::max<int64_t>(1, (nq + 255) / 256), 2048);
-    pcp::Tmp tmp(ctx);
-    double* part = nullptr;
-    PCP_TRY(tmp.get(&part, (size_t)nb * pcp::kAcc));
-    const dim3 block(pcp::kPairBlock);
-    hipLaunchKernelGGL(pcp::k_acc_owned, dim3(nb), block, 0, ctx->stream, T_dev, q_dev, q_stride / sizeof(float), nq,
-                       keys_dev, owner_dev, rank, lo, hi, shard_xyz_dev, shard_stride / sizeof(float), part);
-    hipLaunchKernelGGL(pcp::k_sum_partials, dim3(1), block, 0, ctx->stream, (const double*)part, nb, acc_dev);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
-}
-
-int pcp_slab_guard(pcp_ctx* ctx, const double* T_dev, const double box[6], double lo, double hi, int* flag_dev) {
-    if (!ctx || !T_dev || !box || !flag_dev) return PCP_ERR_ARG;
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(pcp::k_slab_guard, dim3(1), dim3(1), 0, ctx->stream, T_dev, box[0], box[1], box[2], box[3],
-                       box[4], box[5], lo, hi, flag_dev);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
-}
-
-int pcp_icp_accumulate_keys(pcp_ctx* ctx, pcp_icp* icp, const double T[16], const uint64_t* keys_dev,
-                            int64_t lo, int64_t hi, const float* shard_xyz_dev, size_t shard_stride_bytes,
-                            double* acc_dev) {
-    if (!ctx || !icp || !T || !keys_dev || !acc_dev || lo < 0 || hi < lo || (hi > lo && !shard_xyz_dev))
-        return PCP_ERR_ARG;
-    if (shard_stride_bytes == 0) shard_stride_bytes = 3 * sizeof(float);
-    if (shard_stride_bytes % sizeof(float)) return pcp::set_error(ctx, PCP_ERR_ARG, "shard stride must be whole floats");
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    const int nb = (int)std::min<int64_t>(std::max<int64_t>(1, (icp->nq + 255) / 256), icp->nb_fast + icp->nb_ring);
-    const dim3 block(pcp::kPairBlock);
-    hipLaunchKernelGGL(pcp::k_acc_keys, dim3(nb), block, 0, ctx->stream, icp->q, icp->qidx, icp->nq, keys_dev,
-                       (uint64_t)lo, (uint64_t)hi, shard_xyz_dev, shard_stride_bytes / sizeof(float), pcp::pose32(T),
-                       icp->partials);
-    hipLaunchKernelGGL(pcp::k_sum_partials, dim3(1), block, 0, ctx->stream, (const double*)icp->partials, nb, acc_dev);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
-}
-
 int pcp_icp_solve(const double acc[24], int do_scale, double dT[16]) {
     if (!acc || !dT) return PCP_ERR_ARG;
     return pcp::icp_solve(acc, do_scale, dT);
@@ -2570,8 +1632,9 @@ int pcp_icp_run(pcp_ctx* ctx, pcp_icp* icp, double T[16], float rmax, int iters,
     icp->ctx = ctx;
     double e = -1.0, ms_total = 0.0;
     int launches = 0;
+    const pcp::LaunchReq rq = pcp::LaunchReq::host(T, rmax, icp->acc);  // (T is updated in place below)
     for (int it = 0; it < iters; it++) {
-        PCP_TRY(pcp::icp_launch(icp, T, rmax, icp->acc, nullptr, nullptr));
+        PCP_TRY(pcp::icp_launch(icp, rq));
         double acc[24];
         PCP_HIP(ctx, hipMemcpyAsync(acc, icp->acc, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
         PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2610,7 +1673,7 @@ int pcp_icp_step_dev(pcp_ctx* ctx, pcp_icp* icp, const double* T_dev, float rmax
     if (!ctx || !icp || !T_dev || !acc_dev || !(rmax >= 0.f)) return PCP_ERR_ARG;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     icp->ctx = ctx;
-    return pcp::icp_launch(icp, nullptr, rmax, acc_dev, nullptr, nullptr, T_dev);
+    return pcp::icp_launch(icp, pcp::LaunchReq::dev(T_dev, rmax, acc_dev));
 }
 
 int pcp_icp_solve_dev(pcp_ctx* ctx, const double* acc_dev, int do_scale, double* T_dev, double* stats_dev) {
@@ -2626,8 +1689,9 @@ int pcp_icp_run_dev(pcp_ctx* ctx, pcp_icp* icp, double* T_dev, float rmax, int i
     if (!ctx || !icp || !T_dev || !stats_dev || iters < 0 || !(rmax >= 0.f)) return PCP_ERR_ARG;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     icp->ctx = ctx;
+    const pcp::LaunchReq rq = pcp::LaunchReq::dev(T_dev, rmax, icp->acc);
     for (int it = 0; it < iters; it++) {
-        PCP_TRY(pcp::icp_launch(icp, nullptr, rmax, icp->acc, nullptr, nullptr, T_dev));
+        PCP_TRY(pcp::icp_launch(icp, rq));
         hipLaunchKernelGGL(pcp::k_icp_solve_dev, dim3(1), dim3(1), 0, ctx->stream, (const double*)icp->acc, do_scale,
                            T_dev, stats_dev);
     }
@@ -2668,7 +1732,7 @@ int pcp_icp_last_lookahead(const pcp_icp* icp, double* beta, double* max_offset_
     pcp_ctx* ctx = icp->ctx;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     float w[2] = {0.f, 0.f};
-    PCP_HIP(ctx, hipMemcpyAsync(w, icp->pose_dev + pcp::kPoseBeta, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipMemcpyAsync(w, &icp->pose_dev->beta, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
     PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (beta) *beta = w[0];
     if (max_offset_m) *max_offset_m = w[1];
@@ -2689,7 +1753,7 @@ int pcp_icp_pilot_info(const pcp_icp* icp, int64_t* stride, int64_t* chunks, int
     pcp_ctx* ctx = icp->ctx;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     float w = -1.f;
-    PCP_HIP(ctx, hipMemcpyAsync(&w, icp->pose_dev + pcp::kPilotPairs, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipMemcpyAsync(&w, &icp->pose_dev->pilot_pairs, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
     PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const bool ran = icp->launches > 0 && w >= 0.f;
     const int64_t nch = (icp->nq + 63) / 64, s = std::max<int64_t>(1, nch / pcp::kPilotChunks);

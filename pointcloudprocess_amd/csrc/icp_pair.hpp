@@ -1,7 +1,7 @@
 // What a consumer does with one 64-bit correspondence key and the pair it names, written once: the
 // key's layout, the fp32 cast of a pose, the usable-pair test / residual / 30 terms of the
 // point-to-plane accumulation (pcp.h I2, I3b, I5), the 23 terms of the Kabsch accumulation, and the
-// fixed-order block reductions behind them.  icp.hip, icp_plane.hip, icp_trim.hip and
+// fixed-order block reductions behind them.  icp.hip, icp_shard.hip, icp_plane.hip, icp_trim.hip and
 // icp_batch.hip build their key kernels from these, so "the same arithmetic" is the same text.
 #pragma once
 #include "icp_plane_solve.hpp"

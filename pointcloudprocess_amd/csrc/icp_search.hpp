@@ -8,13 +8,18 @@
 
 namespace pcp {
 
-// q' = R q + t: x' = fmaf(R02,z,fmaf(R01,y,fmaf(R00,x,t0))).  A: anything with float R[9]
-// (row-major) and t[3].
+// q' = R q + t: x' = fmaf(R02,z,fmaf(R01,y,fmaf(R00,x,t0))), R row-major.  The one place the chain
+// is written: its nesting order is the bit-exact contract with the oracle.
+__device__ __forceinline__ void xform_rt(const float (&R)[9], const float (&t)[3], const float4 q, float& x, float& y,
+                                         float& z) {
+    x = __fmaf_rn(R[2], q.z, __fmaf_rn(R[1], q.y, __fmaf_rn(R[0], q.x, t[0])));
+    y = __fmaf_rn(R[5], q.z, __fmaf_rn(R[4], q.y, __fmaf_rn(R[3], q.x, t[1])));
+    z = __fmaf_rn(R[8], q.z, __fmaf_rn(R[7], q.y, __fmaf_rn(R[6], q.x, t[2])));
+}
+// under a's pose.  A: anything with float R[9] and t[3].
 template <typename A>
 __device__ __forceinline__ void xform(const A& a, const float4 q, float& x, float& y, float& z) {
-    x = __fmaf_rn(a.R[2], q.z, __fmaf_rn(a.R[1], q.y, __fmaf_rn(a.R[0], q.x, a.t[0])));
-    y = __fmaf_rn(a.R[5], q.z, __fmaf_rn(a.R[4], q.y, __fmaf_rn(a.R[3], q.x, a.t[1])));
-    z = __fmaf_rn(a.R[8], q.z, __fmaf_rn(a.R[7], q.y, __fmaf_rn(a.R[6], q.x, a.t[2])));
+    xform_rt(a.R, a.t, q, x, y, z);
 }
 // the same chain for a query read from a caller's strided float array
 template <typename A>

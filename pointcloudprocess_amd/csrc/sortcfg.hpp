@@ -1,5 +1,5 @@
 // The (u32 cell key, 16-byte record) sorts of the fp32 ICP index build (grid.hip) and of the ICP
-// query set (icp.hip) keep rocPRIM's tuned gfx950 default (8 key bits per pass: 4 passes for
+// query set (icp_create.hip) keep rocPRIM's tuned gfx950 default (8 key bits per pass: 4 passes for
 // the ~30-bit cell keys).  Also the one helper every plain sort site uses.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>

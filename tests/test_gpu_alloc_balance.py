@@ -247,6 +247,19 @@ def test_icp(ctx, cloud):
             ops.accumulate_owned(ctx, T_dev, q, keys, owner, 0, 0, len(xyz), tgt)
         icp.close()
         ix.close()
+    with balanced(ctx, "pilot forced on + captured graph"):
+        ix = ops.GridIndex(ctx, tgt, cell_size=0.5)
+        icp = ops.ICP(ix, q)
+        icp.set_options(pilot=True)  # the pilot's accumulators are a block of the handle's
+        T_dev, stats = icp.new_pose()
+        icp.run_dev(T_dev, stats, 0.5, 3)
+        icp.close()
+        icp = ops.ICP(ix, q)
+        icp.set_options(graph=True)  # captured at launch 2, replayed at launch 3, torn down by close
+        T_dev, stats = icp.new_pose()
+        icp.run_dev(T_dev, stats, 0.5, 4)
+        icp.close()
+        ix.close()
     with balanced(ctx, "icp_create_with_target"):
         icp = ops.ICP.with_target(ctx, tgt, q, 0.5)
         icp.run(np.eye(4), 0.5, 2)
