@@ -701,9 +701,9 @@ int pcp_get_rot_icp_plane_rtrimmed(pcp_ctx* ctx, const void* src_aos48_dev, int6
  *   whatever nseg is, and poses bit-identical to calling the three entries in turn.  The plane
  *   table's size must be the target index's caller size (PCP_ERR_ARG otherwise).
  *
- * Not here: the point-to-point minimisation.  The trims of I3 / I3b per segment, and the trimmed
- * loops, are I5b below; pcp_icp_trim_keys itself over a batch's keys takes ONE quantile across all
- * segments, not one per segment. */
+ * Not here: the trims of I3 / I3b per segment, and the trimmed loops, are I5b below; the
+ * point-to-point minimisation over a batch is I5c; pcp_icp_trim_keys itself over a batch's keys
+ * takes ONE quantile across all segments, not one per segment. */
 typedef struct pcp_icp_batch pcp_icp_batch;
 int pcp_icp_batch_create(pcp_ctx* ctx, const pcp_index* target, const float* q_dev, size_t q_stride_bytes,
                          int64_t nq, const int64_t* seg_offsets_host /* nseg + 1 */, int nseg,
@@ -780,7 +780,8 @@ int pcp_icp_batch_run_plane_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const pcp_ic
  *   the others carry on, and a frozen segment is still trimmed every iteration.
  *
  * Not here: per-segment frac, mult or d_floor; a select split over several workgroups for one very
- * large segment; the point-to-point minimisation; pcp_get_rot_icp_*-style wrappers. */
+ * large segment; pcp_get_rot_icp_*-style wrappers.  The point-to-point loops, plain and with the
+ * point trim, are I5c. */
 int pcp_icp_batch_trim_keys(pcp_ctx* ctx, pcp_icp_batch* batch, const uint64_t* keys_dev /* nq, ORIGINAL order */,
                             float frac, float mult, float d_floor,
                             uint64_t* keys_out_dev, uint64_t* trim_dev /* nseg x 4 */);
@@ -796,6 +797,78 @@ int pcp_icp_batch_run_plane_rtrimmed_dev(pcp_ctx* ctx, pcp_icp_batch* batch, con
                                          double* T_dev, float rmax, float frac, float mult, float d_floor,
                                          int iters, double* stats_dev /* nseg x 4 */,
                                          uint64_t* trim_dev /* nseg x 4: last iteration */);
+
+/* ----------------------------------------------------------------------- I5c: point-to-point over a batch
+ * The get_rot_icp contract (point-to-point, with do_scale: pcp_icp_solve, pcp_icp_run_dev) for
+ * every segment of a pcp_icp_batch: the ported callers re-register every frame of a span through
+ * get_rot_icp (do_mul_frame_icp with is_do_sep_icp), one handle and about thirteen dependent
+ * launches per iteration each; here an iteration is three launches whatever nseg is, or six with
+ * the per-segment point trim of I5b.  Nothing is fused: a loop is its entries in turn.
+ *
+ * Target points.  target_xyz_dev is the fp32 cloud the target index was built from, point j at
+ *   its CALLER index (stride 0 = 12): the fp32 index keeps no caller-order copy, so the caller
+ *   passes it, as pcp_icp_accumulate_owned takes its shard.  pcp_icp_batch_accumulate skips, and
+ *   never reads, a key whose index is >= n_target; in the loops n_target must be the index's caller
+ *   size (PCP_ERR_ARG otherwise).
+ *
+ * pcp_icp_batch_accumulate: row s of acc_dev (nseg x PCP_ICP_ACC) is the 24 accumulators of
+ *   pcp_icp_solve over segment s's queries whose key (keys_dev: nq keys, ORIGINAL order) is not
+ *   INT64_MAX: n, A = sum q' (3), B = sum p (3), AB = sum q' p^T (9, row-major), AA = sum q' q'^T
+ *   (upper triangle 00 01 02 11 12 22), D = sum d2, with
+ *     q' = the fp32 fmaf chain of I5 at the fp32 cast of the pose T_dev + 16 s (the handle's own
+ *       copy of the query), p = target_xyz[j], both widened to fp64: every product of widened fp32
+ *       values is exact, and [22] adds the key's fp32 d2 (its high word);
+ *     [23] (pcp_icp_step_dev's fallback count) is written 0.
+ *   An empty segment writes 24 zeros.  The order of the sum is fixed by the handle alone: per
+ *   64-slot chunk of the segment's sorted, padded queries a butterfly over lane offsets 32 .. 1;
+ *   then the segment's chunks in eight interleaved groups (group g adds chunks g, g + 8, .. in
+ *   order); then the groups in order.  The result is bit for bit the same on every run, uses no
+ *   float atomics and is independent of the other segments.  It agrees with
+ *   pcp_icp_accumulate_owned over the same pairs to rounding, not bit for bit.
+ *
+ * pcp_icp_batch_solve_dev: device thread s runs exactly pcp_icp_solve_dev's step on row s of
+ *   acc_dev, T_dev + 16 s and stats_dev + 4 s (stats as there: status, RMS point distance of the
+ *   last solved step, running sum of [23], steps solved; zeroed by the caller).  It returns at once
+ *   when stats[4 s] < 0; stats[4 s + 2] += acc[23]; then pcp_icp_solve(acc, do_scale) -- rank 0,
+ *   the planar and collinear completions, the refusals on n < 3 or a non-finite sum, all as there.
+ *   On refusal stats[4 s] = -1 and nothing else of that segment changes; otherwise
+ *   stats[4 s + 1] = sqrt(acc[22] / acc[0]), stats[4 s + 3] += 1 and T_s <- dT * T_s.  do_scale is
+ *   one flag for all segments.  A refused segment freezes alone; the others carry on.
+ *
+ * pcp_icp_batch_run_dev = iters x (pcp_icp_batch_keys_dev, accumulate, sum + solve) on the context's
+ *   stream: three launches per iteration whatever nseg is, no host round trip and no allocation
+ *   inside the loop.  Poses and stats are bit-identical to calling the three entries in turn.
+ *
+ * pcp_icp_batch_run_trimmed_dev = iters x (keys, pcp_icp_batch_trim_keys in place, accumulate, sum +
+ *   solve): six launches per iteration, bit-identical to the four entries in turn.  trim_dev
+ *   receives the last iteration's rows (nseg x 4, as I5b) and is untouched when iters == 0.  A
+ *   frozen segment is still searched and trimmed every iteration.
+ *
+ * Arguments.  PCP_ERR_ARG for: a null context or batch; a null T_dev, acc_dev, stats_dev or trim_dev
+ *   with nseg > 0; null keys with nq > 0; a null target_xyz_dev with n_target > 0; n_target < 0; a
+ *   stride that is not a whole number of floats or is below 12; nseg outside [0, 65535] in the solve
+ *   entry; iters < 0; !(rmax >= 0); frac, mult and d_floor as I5b.  Every check comes before the
+ *   first device call and a rejected call writes nothing.  nseg == 0 returns PCP_OK and writes
+ *   nothing.  Temporaries (the loop's keys, the chunks' partial sums, the trim's statistic) come from
+ *   the per-call guard, so pcp_ctx_alloc_stats balances on every path.
+ *
+ * Not here: a fused search + accumulate kernel; per-segment do_scale or trim parameters; the
+ * plane-residual trim (it needs a plane table); pcp_get_rot_icp-style wrappers with fp64 centring
+ * (the caller centres, as for every fp32 ICP entry). */
+#define PCP_ICP_ACC 24
+int pcp_icp_batch_accumulate(pcp_ctx* ctx, pcp_icp_batch* batch, const double* T_dev /* nseg x 16 */,
+                             const uint64_t* keys_dev /* nq, ORIGINAL order */,
+                             const float* target_xyz_dev, size_t t_stride_bytes, int64_t n_target,
+                             double* acc_dev /* nseg x 24 */);
+int pcp_icp_batch_solve_dev(pcp_ctx* ctx, const double* acc_dev, int nseg, int do_scale,
+                            double* T_dev, double* stats_dev /* nseg x 4 */);
+int pcp_icp_batch_run_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const float* target_xyz_dev, size_t t_stride_bytes,
+                          int64_t n_target, double* T_dev, float rmax, int iters, int do_scale,
+                          double* stats_dev /* nseg x 4, zeroed by the caller */);
+int pcp_icp_batch_run_trimmed_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const float* target_xyz_dev,
+                                  size_t t_stride_bytes, int64_t n_target, double* T_dev, float rmax,
+                                  float frac, float mult, float d_floor, int iters, int do_scale,
+                                  double* stats_dev, uint64_t* trim_dev /* nseg x 4: last iteration */);
 
 /* ----------------------------------------------------------------------- I4: pose lines
  * Host-only (no device work): n frames' poses as row-major 4x4 doubles, rots[16 * i].

@@ -144,6 +144,11 @@ SIGNATURES = [
     ("pcp_icp_batch_trim_keys_plane", _i32, [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     ("pcp_icp_batch_run_plane_trimmed_dev", _i32, [_vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
     ("pcp_icp_batch_run_plane_rtrimmed_dev", _i32, [_vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    ("pcp_icp_batch_accumulate", _i32, [_vp, _vp, _vp, _vp, _vp, _sz, _i64, _vp]),
+    ("pcp_icp_batch_solve_dev", _i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    ("pcp_icp_batch_run_dev", _i32, [_vp, _vp, _vp, _sz, _i64, _vp, _f32, _i32, _i32, _vp]),
+    ("pcp_icp_batch_run_trimmed_dev", _i32, [_vp, _vp, _vp, _sz, _i64, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp,
+                                             _vp]),
 ]
 
 _lib = None

@@ -1,6 +1,7 @@
-// What icp_batch.hip and icp_batch_trim.hip share of a batch handle (include/pcp.h, I5 / I5b): the
-// handle with its padded chunk layout, the chunk grid, and the launches of the three kernels of an
-// untrimmed iteration (defined in icp_batch.hip), which the trimmed loops put their trim between.
+// What icp_batch.hip, icp_batch_trim.hip and icp_batch_p2p.hip share of a batch handle
+// (include/pcp.h, I5 / I5b / I5c): the handle with its padded chunk layout, the chunk grid, and the
+// launches an iteration is put together from -- the search and the plane pair (icp_batch.hip), the
+// per-segment trim (icp_batch_trim.hip), the point-to-point pair (icp_batch_p2p.hip).
 #pragma once
 #include "icp_pair.hpp"
 
@@ -32,5 +33,22 @@ void batch_launch_acc(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev,
 // T + 16 s, stats + 4 s when T is given
 void batch_launch_sum_solve(pcp_ctx* ctx, const pcp_icp_batch* b, const double* part, double* acc_out, double* T,
                             double* stats);
+
+// the per-segment trim of I5b on ctx's stream, three launches (icp_batch_trim.hip): skeys is 64 * nch
+// keys of the caller's guard memory; planes == nullptr ranks the keys' own high words and reads no
+// pose; out == keys trims in place
+void launch_trim(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, const uint64_t* keys,
+                 const pcp_icp_planes* planes, float frac, float mult, float d_floor, uint64_t* out, uint64_t* trim,
+                 uint64_t* skeys);
+
+// the point-to-point pair of launches (icp_batch_p2p.hip, I5c), as the plane pair above: the chunks'
+// 24 Kabsch partials from the caller's target cloud (t_stride_f floats apart, n_target points; needs
+// nch > 0), then per segment their sum -> row s of acc_out when given and the Kabsch step on
+// T + 16 s, stats + 4 s when T is given
+void batch_launch_acc_kabsch(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, const uint64_t* keys,
+                             const float* target_xyz, size_t t_stride_f, int64_t n_target,
+                             double* part /* nch x 24 */);
+void batch_launch_sum_solve_kabsch(pcp_ctx* ctx, const pcp_icp_batch* b, const double* part, double* acc_out,
+                                   int do_scale, double* T, double* stats);
 
 }  // namespace pcp

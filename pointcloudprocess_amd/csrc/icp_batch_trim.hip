@@ -189,8 +189,11 @@ __global__ void __launch_bounds__(kBB) k_bt_filter(const float4* qrec, const int
     if (lane == 0 && cnt) atomicAdd((unsigned long long*)&row[1], (unsigned long long)cnt);
 }
 
+}  // namespace
+
 // the trim of every segment on ctx's stream: skeys is 64 * nch keys of the caller's guard memory;
-// planes == nullptr ranks the keys' own high words
+// planes == nullptr ranks the keys' own high words (declared in icp_batch.hpp: the point-to-point
+// trimmed loop of icp_batch_p2p.hip runs it too)
 void launch_trim(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, const uint64_t* keys,
                  const pcp_icp_planes* planes, float frac, float mult, float d_floor, uint64_t* out, uint64_t* trim,
                  uint64_t* skeys) {
@@ -217,6 +220,8 @@ void launch_trim(pcp_ctx* ctx, const pcp_icp_batch* b, const double* T_dev, cons
                                (const uint64_t*)skeys, out, inplace, trim);
     }
 }
+
+namespace {
 
 // the argument rules the two trims share; planes and T_dev are checked by the plane trim's caller
 bool trim_call_ok(const pcp_ctx* ctx, const pcp_icp_batch* b, const uint64_t* keys, float frac, float mult,

@@ -624,7 +624,10 @@ class ICPBatch:
     device pose per segment, three launches per point-to-plane iteration whatever B is.  q: (n, >= 3)
     fp32 device tensor; seg_offsets: B + 1 non-decreasing integers from 0 to n (segment s is
     q[seg_offsets[s]:seg_offsets[s + 1]]).  Keys are in q's order.  The trimmed loops (pcp.h I5b) trim
-    every segment by its own quantile and take six launches per iteration, again whatever B is."""
+    every segment by its own quantile and take six launches per iteration, again whatever B is.  The
+    point-to-point loops (pcp.h I5c: accumulate, solve_dev, run_dev, run_trimmed_dev) minimise the
+    get_rot_icp objective per segment in the same three / six launches; they read the target's points
+    from the cloud the index was built from, which the caller passes."""
 
     def __init__(self, target_index, q, seg_offsets):
         self.index = target_index
@@ -742,6 +745,61 @@ class ICPBatch:
         as there."""
         return self._run_trimmed(self.ctx.lib.pcp_icp_batch_run_plane_rtrimmed_dev, planes, T_dev, stats, rmax, frac,
                                  mult, d_floor, iters, trim)
+
+    # ---- point-to-point (pcp.h I5c): the get_rot_icp contract per segment
+    @staticmethod
+    def _target(target_xyz):
+        """(pointer, stride in bytes, points) of the target cloud, (n, >= 3) fp32 at caller index."""
+        assert target_xyz.dtype == torch.float32 and target_xyz.dim() == 2 and target_xyz.shape[1] >= 3
+        assert target_xyz.stride(1) == 1 or target_xyz.shape[0] == 0
+        n = target_xyz.shape[0]
+        return _ptr(target_xyz) if n else None, target_xyz.stride(0) * target_xyz.element_size() if n else 0, n
+
+    def accumulate(self, T_dev, keys, target_xyz, acc=None):
+        """(B, 24): per segment the Kabsch accumulators of pcp_icp_solve over its pairs; target_xyz:
+        the cloud the target index was built from.  [23] is 0."""
+        ctx = self.ctx
+        acc = torch.zeros((self.nseg, 24), dtype=torch.float64, device=ctx.device) if acc is None else acc
+        assert acc.dtype == torch.float64 and acc.numel() >= 24 * self.nseg and acc.is_contiguous()
+        assert keys.dtype == torch.int64 and keys.numel() >= self.nq and keys.is_contiguous()
+        self._check_poses(T_dev)
+        tp, ts, tn = self._target(target_xyz)
+        ctx.check(ctx.lib.pcp_icp_batch_accumulate(ctx.h, self.h, _ptr(T_dev), _ptr(keys), tp, ts, tn, _ptr(acc)))
+        return acc
+
+    def solve_dev(self, acc, T_dev, stats, do_scale=False):
+        """Per segment ICP.solve_dev: T_dev[s] <- dT_s * T_dev[s]; a refused solve latches
+        stats[s, 0] = -1 and freezes that segment's pose only."""
+        ctx = self.ctx
+        assert acc.dtype == torch.float64 and acc.numel() >= 24 * self.nseg and acc.is_contiguous()
+        self._check_poses(T_dev, stats)
+        ctx.check(ctx.lib.pcp_icp_batch_solve_dev(ctx.h, _ptr(acc), self.nseg, int(do_scale), _ptr(T_dev),
+                                                  _ptr(stats)))
+
+    def run_dev(self, target_xyz, T_dev, stats, rmax, iters, do_scale=False):
+        """iters x (keys_dev, accumulate, solve_dev) with no host round trip: three launches per
+        iteration whatever B is."""
+        ctx = self.ctx
+        self._check_poses(T_dev, stats)
+        tp, ts, tn = self._target(target_xyz)
+        ctx.check(ctx.lib.pcp_icp_batch_run_dev(ctx.h, self.h, tp, ts, tn, _ptr(T_dev), float(rmax), int(iters),
+                                                int(do_scale), _ptr(stats)))
+
+    def run_trimmed_dev(self, target_xyz, T_dev, stats, rmax, frac, mult=1.0, d_floor=0.0, iters=4, do_scale=False,
+                        trim=None):
+        """run_dev with trim_keys(frac, mult, d_floor) in place between the keys and the accumulation
+        of every iteration: six launches per iteration.  A segment left with fewer than 3 pairs
+        freezes alone.  Returns trim: the last iteration's (B, 4) rows [m, kept, sel, bits of cut]."""
+        ctx = self.ctx
+        self._check_poses(T_dev, stats)
+        trim = torch.zeros((self.nseg, 4), dtype=torch.int64, device=ctx.device) if trim is None else trim
+        assert trim.dtype == torch.int64 and trim.numel() >= 4 * self.nseg and trim.is_contiguous()
+        tp, ts, tn = self._target(target_xyz)
+        ctx.check(ctx.lib.pcp_icp_batch_run_trimmed_dev(ctx.h, self.h, tp, ts, tn, _ptr(T_dev), float(rmax),
+                                                        float(frac), float(mult), float(d_floor), int(iters),
+                                                        int(do_scale), _ptr(stats),
+                                                        _ptr(trim) if self.nseg else None))
+        return trim
 
     def close(self):
         if getattr(self, "h", None):

@@ -26,8 +26,13 @@ rtrim_ref.SCENE_RTRIM: (a) ICPBatch create + run_plane_rtrimmed_dev, (b) segs x 
 run_plane_rtrimmed_dev).  The entries then also time the batch's trim alone and the untrimmed
 run_plane_dev on the same batch, and every window's error is listed.
 
+With --p2p both legs minimise the point-to-point objective of get_rot_icp (pcp.h I5c): (a) ICPBatch
+create + run_dev, (b) segs x (ICP create + run_dev), --iters iterations each (4, or 20 = the
+get_rot_icp default); no normals and no plane table are built, and the entries are keys_dev,
+accumulate, solve_dev and one iteration of run_dev.
+
     python tools/icp_batch_ab.py [--segs 64 --per 20000 --window 20] [--reps 5] [--no-loop] [--trace]
-                                 [--trimmed]
+                                 [--trimmed | --p2p] [--iters 4]
 """
 import argparse
 import json
@@ -107,15 +112,22 @@ def main():
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--trimmed", action="store_true", help="25 %% clutter per window, residual-trimmed loops")
+    ap.add_argument("--p2p", action="store_true", help="the point-to-point loops (run_dev) on both legs")
+    ap.add_argument("--iters", type=int, default=ITERS)
     args = ap.parse_args()
+    if args.p2p and args.trimmed:
+        raise SystemExit("--p2p and --trimmed exclude each other")
+    iters_all = args.iters
     ctx = ops.Context(0)
     dev = ctx.device
     tgt = synth.street_scene(args.target, 4101, device=dev)
-    ix64 = ops.GridIndex(ctx, tgt.double())
-    rows = ops.normals_knn(ix64, 16)
-    ix64.close()
     index = ops.GridIndex(ctx, tgt, cell_size=0.25)
-    planes = ops.IcpPlanes(ctx, tgt, rows)
+    planes = None
+    if not args.p2p:
+        ix64 = ops.GridIndex(ctx, tgt.double())
+        rows = ops.normals_knn(ix64, 16)
+        ix64.close()
+        planes = ops.IcpPlanes(ctx, tgt, rows)
     q, off, T_true = make_segments(args.scene, args.segs, args.per, args.window, dev,
                                    clutter=0.25 if args.trimmed else 0.0)
     B = args.segs
@@ -131,17 +143,21 @@ def main():
     def reset():
         T_b.copy_(eye); st_b.zero_(); T_l.copy_(eye); st_l.zero_()
 
-    def run_batch(b, iters=ITERS):
-        if args.trimmed:
+    def run_batch(b, iters=iters_all):
+        if args.p2p:
+            b.run_dev(tgt, T_b, st_b, RMAX, iters)
+        elif args.trimmed:
             b.run_plane_rtrimmed_dev(planes, T_b, st_b, RMAX, *RT, iters=iters, trim=tr_b)
         else:
             b.run_plane_dev(planes, T_b, st_b, RMAX, iters)
 
     def run_single(h, s):
-        if args.trimmed:
-            h.run_plane_rtrimmed_dev(planes, segq[s], T_l[s], st_l[s], RMAX, *RT, iters=ITERS, trim=tr_l[s])
+        if args.p2p:
+            h.run_dev(T_l[s], st_l[s], RMAX, iters_all)
+        elif args.trimmed:
+            h.run_plane_rtrimmed_dev(planes, segq[s], T_l[s], st_l[s], RMAX, *RT, iters=iters_all, trim=tr_l[s])
         else:
-            h.run_plane_dev(planes, segq[s], T_l[s], st_l[s], RMAX, ITERS)
+            h.run_plane_dev(planes, segq[s], T_l[s], st_l[s], RMAX, iters_all)
 
     def batch_total():
         b = ops.ICPBatch(index, q, off)
@@ -156,8 +172,8 @@ def main():
             hs.append(h)
         return hs
 
-    res = {"segs": B, "per": args.per, "window_m": args.window, "target": args.target, "iters": ITERS, "rmax": RMAX,
-           "reps": args.reps, "trimmed": list(RT) if args.trimmed else None, "build": ctx.lib.pcp_build_id().decode()}
+    res = {"segs": B, "per": args.per, "window_m": args.window, "target": args.target, "iters": iters_all, "rmax": RMAX,
+           "reps": args.reps, "p2p": bool(args.p2p), "trimmed": list(RT) if args.trimmed else None, "build": ctx.lib.pcp_build_id().decode()}
     if args.trace:
         for _ in range(2):
             reset()
@@ -222,16 +238,20 @@ def main():
     # the batch's entries alone, from the identity (the first iteration's work)
     b = ops.ICPBatch(index, q, off)
     keys = torch.empty(q.shape[0], dtype=torch.int64, device=dev)
-    acc = torch.zeros((B, 30), dtype=torch.float64, device=dev)
-    entry = {"keys_dev": lambda: b.keys_dev(eye, RMAX, out=keys),
-             "accumulate_plane": lambda: b.accumulate_plane(eye, keys, planes, acc=acc),
-             "solve_plane_dev": lambda: b.solve_plane_dev(acc, T_b, st_b),
-             "run_1_iteration": lambda: run_batch(b, 1)}
+    acc = torch.zeros((B, 24 if args.p2p else 30), dtype=torch.float64, device=dev)
+    entry = {"keys_dev": lambda: b.keys_dev(eye, RMAX, out=keys)}
+    if args.p2p:
+        entry["accumulate"] = lambda: b.accumulate(eye, keys, tgt, acc=acc)
+        entry["solve_dev"] = lambda: b.solve_dev(acc, T_b, st_b)
+    else:
+        entry["accumulate_plane"] = lambda: b.accumulate_plane(eye, keys, planes, acc=acc)
+        entry["solve_plane_dev"] = lambda: b.solve_plane_dev(acc, T_b, st_b)
+    entry["run_1_iteration"] = lambda: run_batch(b, 1)
     if args.trimmed:
         tkeys = torch.empty_like(keys)
         entry["trim_keys_plane"] = lambda: b.trim_keys_plane(eye, keys, planes, *RT, out=tkeys)
         entry["run_rtrimmed"] = lambda: run_batch(b)
-        entry["run_untrimmed_same_batch"] = lambda: b.run_plane_dev(planes, T_b, st_b, RMAX, ITERS)
+        entry["run_untrimmed_same_batch"] = lambda: b.run_plane_dev(planes, T_b, st_b, RMAX, iters_all)
     ems = {k: [] for k in entry}
     for r in range(args.reps + 1):
         for k, fn in entry.items():
@@ -243,7 +263,8 @@ def main():
     res["keyed_fraction_first_iteration"] = float((keys != np.iinfo(np.int64).max).float().mean().item())
     b.close()
     print(json.dumps(res))
-    planes.close()
+    if planes is not None:
+        planes.close()
     index.close()
 
 
