@@ -120,6 +120,12 @@ const void* pcp_index_sorted_points(const pcp_index* index);
  * past the clamped k are -1 / +inf.  out_d2_dev may be NULL (indices only). */
 int pcp_knn(pcp_ctx* ctx, const pcp_index* index, const double* q_dev, size_t q_stride_bytes,
             int64_t nq, int k, int32_t* out_idx_dev, double* out_d2_dev);
+/* Queries of the last pcp_knn on this context (pcp_nearest_query's included) whose k-th
+ * neighbour lay beyond the near pass's cell rings and were answered by the exact
+ * wave-per-query pass (diagnostic).  No reference counterpart.  0 when the call returned
+ * before searching (argument error, nq == 0, PCP_ERR_UNSUPPORTED).  pcp_knn itself stays
+ * asynchronous; this call waits for the stream. */
+int pcp_knn_last_far(pcp_ctx* ctx, int64_t* n);
 
 /* C5 (BASELINE configs[4]): fp16 cell-relative index + radius search with fused normals.
  * pcp_index_build_h16 sorts the cloud (fp32 xyz) into cells of `cell_size` (1 mm <= h <= 0.5 m:

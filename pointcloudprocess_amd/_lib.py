@@ -45,6 +45,7 @@ SIGNATURES = [
     ("pcp_index_cells", _i64, [_vp]),
     ("pcp_index_sorted_points", _vp, [_vp]),
     ("pcp_knn", _i32, [_vp, _vp, _vp, _sz, _i64, _i32, _vp, _vp]),
+    ("pcp_knn_last_far", _i32, [_vp, _P(_i64)]),
     ("pcp_radius_count", _i32, [_vp, _vp, _vp, _sz, _i64, _f64, _u32, _vp]),
     ("pcp_radius_fill", _i32, [_vp, _vp, _vp, _sz, _i64, _f64, _u32, _vp, _vp, _vp]),
     ("pcp_index_build_h16", _i32, [_vp, _vp, _sz, _i64, _f64, _P(_vp)]),

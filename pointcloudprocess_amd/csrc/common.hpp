@@ -30,6 +30,11 @@ struct pcp_ctx {
     // grid {near pass's list, unused}
     uint32_t* nrm_deferred = nullptr;
     int nrm_mode = 0;
+    // deferred queries of the last pcp_knn (pcp_knn_last_far): one device word the call copies
+    // its far list's counter into, stream-ordered; allocated on first use.  knn_far_set: false
+    // when the call returned before searching
+    uint32_t* knn_far = nullptr;
+    bool knn_far_set = false;
     // look-back scan state (scan.hip): per-tile status words tagged with the call's epoch, so
     // no clearing pass is needed per call; [tiles] u64 status, then the tile counter and total
     uint64_t* scan_status = nullptr;

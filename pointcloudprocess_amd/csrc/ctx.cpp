@@ -203,9 +203,11 @@ int pcp_ctx_destroy(pcp_ctx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->scan_status) (void)hipFree(ctx->scan_status);
     if (ctx->nrm_deferred) (void)hipFree(ctx->nrm_deferred);
+    if (ctx->knn_far) (void)hipFree(ctx->knn_far);
     ctx->scratch = nullptr;
     ctx->scan_status = nullptr;
     ctx->nrm_deferred = nullptr;
+    ctx->knn_far = nullptr;
     pcp::cache_release(ctx);
     ctx->closing = true;
     if (ctx->live == 0) pcp::ctx_finish(ctx);  // else the last object's destroy finishes it

@@ -548,10 +548,12 @@ __global__ __launch_bounds__(kB) void k_knn_coop(GridDesc g, const double4* pts,
         double md;
         int mj;
         coop_merge<K>(v, kk, lane, md, mj);
-        if (lane < k) {
-            const bool ok = lane < kk && mj != INT_MAX;
-            oidx[i * k + lane] = ok ? (identity ? mj : mapping[mj]) : -1;
-            if (od2) od2[i * k + lane] = ok ? md : INFINITY;
+        // entry r < kk (<= 64) is lane r's; the lanes stride over the padding [kk, k), which
+        // reaches past the wave when k > 64 over an index of at most 64 points
+        for (int r = lane; r < k; r += 64) {
+            const bool ok = r < kk && mj != INT_MAX;
+            oidx[i * k + r] = ok ? (identity ? mj : mapping[mj]) : -1;
+            if (od2) od2[i * k + r] = ok ? md : INFINITY;
         }
     }
 }
@@ -1645,6 +1647,7 @@ extern "C" {
 
 int pcp_knn(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, int64_t nq, int k,
             int32_t* oidx, double* od2) {
+    if (ctx) ctx->knn_far_set = false;
     PCP_TRY(check_f64_index(ctx, ix));
     if (nq < 0 || k <= 0 || (nq > 0 && (!q || !oidx))) return set_error(ctx, PCP_ERR_ARG, "pcp_knn: bad arguments");
     if (qstride == 0) qstride = 3 * sizeof(double);
@@ -1653,6 +1656,7 @@ int pcp_knn(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, 
     const int K = pick_k(kk);
     if (!K) return set_error(ctx, PCP_ERR_UNSUPPORTED, "pcp_knn: k=%d > 64 not supported yet", k);
     PCP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->knn_far) PCP_HIP(ctx, hipMalloc(&ctx->knn_far, sizeof(uint32_t)));
     const double mc = cell_margin64(ix->g);
     const double4* pts = (const double4*)ix->pts;
     Tmp tmp(ctx);
@@ -1673,6 +1677,21 @@ int pcp_knn(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, 
     }
 #undef LAUNCH_KNN
     PCP_LAUNCH_CHECK(ctx);
+    // the far list's length for pcp_knn_last_far, stream-ordered before the list's block is reused
+    PCP_HIP(ctx, hipMemcpyAsync(ctx->knn_far, fb.f.count, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->knn_far_set = true;
+    return PCP_OK;
+}
+
+int pcp_knn_last_far(pcp_ctx* ctx, int64_t* n) {
+    if (!ctx || !n) return PCP_ERR_ARG;
+    *n = 0;
+    if (!ctx->knn_far_set) return PCP_OK;
+    uint32_t h = 0;
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    PCP_HIP(ctx, hipMemcpyAsync(&h, ctx->knn_far, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n = h;
     return PCP_OK;
 }
 

@@ -134,6 +134,15 @@ def knn(index, q, k):
     return idx, d2
 
 
+def knn_last_far(ctx):
+    """Queries of the last knn (or nearest_query) on ctx that the near pass deferred to the
+    exact wave-per-query pass; 0 when the call returned before searching.  Waits for the
+    stream (diagnostic)."""
+    n = C.c_int64()
+    ctx.check(ctx.lib.pcp_knn_last_far(ctx.h, C.byref(n)))
+    return n.value
+
+
 def radius(index, q, r, max_nn=0):
     """Batch radiusSearch -> CSR (offsets int64 (nq+1), idx int32, d2 float64)."""
     ctx = index.ctx
