@@ -642,7 +642,7 @@ void ora_normals_knn(const ora_kdtree* t, const double* xyz, size_t stride, int 
 /* ---- F3: calculate_plan_parameter_rpca (calculate_feature.cpp:208-368), deterministic */
 
 /* SplitMix64 finaliser of (seed, point, iteration, slot): the build's counter-based stand-in
- * for rand() (:249), identical on the GPU (knn.hip k_rpca) */
+ * for rand() (:249), identical on the GPU (rpca.hip k_rpca) */
 uint32_t ora_rpca_draw(uint64_t seed, uint32_t j, uint32_t it, uint32_t slot) {
     uint64_t z = seed + 0x9E3779B97F4A7C15ull * (((uint64_t)j << 32) | ((uint64_t)it << 2) | slot) + 0x632BE59BD9B4E019ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

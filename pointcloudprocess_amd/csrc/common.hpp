@@ -180,6 +180,9 @@ __device__ __forceinline__ bool finite3(double x, double y, double z) {
 // (fold.hip); s_host[3] = number of points summed (finite ones when !is_dense).
 int seqfold_aos48(pcp_ctx* ctx, const void* p0, int64_t n0, const void* p1, int64_t n1, int is_dense,
                   double s_host[4]);
+// compute3DCentroid over n AoS48 records (cloud.hip): c = the centroid, *count = the points
+// summed; n <= 0 leaves c untouched.  Syncs.
+int centroid_aos48_dev(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, double c[4], uint32_t* count);
 
 // What code that does not include icp_handle.hpp may know of an ICP handle (icp_create.hip): its
 // target index and the number of queries passed to pcp_icp_create (the length of a pcp_icp_keys_dev

@@ -1,139 +1,49 @@
 // Exact fp64 neighbour queries over the uniform-grid index: the FLANN contract of
-// KdTreeFLANN::nearestKSearch / radiusSearch (kd_tree.h:814-845, 863-903), the per-point
-// PCA normals of calculate_feature.cpp:119-206 over kNN neighbourhoods, and the
-// kd_tree_lod KdTree (kd_tree_lod/kd_tree.cpp:29-117).
+// KdTreeFLANN::nearestKSearch (kd_tree.h:814-845) and the per-point PCA normals of
+// calculate_feature.cpp:119-206 over kNN neighbourhoods.  Radius search is radius.hip's, the
+// kd_tree_lod search knn_lod.hip's, the per-segment plane fit plane_fit.hip's; what they share
+// with this file is knn_search.hpp.
 //
 // One lane per query.  The k best (d2, internal j) pairs live in registers (compile-time
 // K, unrolled branch-free insertion) and the ring search (grid.hpp) visits cells nearest
 // first, pruning with the current k-th distance.  d2 is FLANN L2_Simple<double>
 // ((0 + d0^2) + d1^2) + d2^2 with contraction off (the build compiles -ffp-contract=off),
 // so distances are bit-identical to the reference's and ties break on internal j exactly
-// like FLANN's "first found in index order" result set after sorting.
-#include <cfloat>
+// like FLANN's "first found in index order" result set after sorting.  Queries whose k-th
+// neighbour lies past the cell rings go to the wave-per-query far pass (knn_coop.hpp).
 #include <cstdlib>
-#include <climits>
-#include <cmath>
 #include <vector>
 
 #include "sortcfg.hpp"
 
-#include "grid.hpp"
-#include "topk.hpp"
+#include "knn_coop.hpp"
 #include "pca.hpp"
 
 #ifndef PCP_NORMALS_STATS
 #define PCP_NORMALS_STATS 0  // profiling builds: per-phase counters of pcp_normals_knn on stderr
 #endif
+
 namespace pcp {
 namespace {
 
-constexpr int kB = 256;
-
-// pruning margin in cell units: floor() rounding of query and point cell coordinates
-__host__ __device__ inline double cell_margin64(const GridDesc& g) {
-    const int nmax = g.n[0] > g.n[1] ? (g.n[0] > g.n[2] ? g.n[0] : g.n[2]) : (g.n[1] > g.n[2] ? g.n[1] : g.n[2]);
-    return 1e-9 + 8e-16 * (double)nmax;
-}
-
-// Candidates of a cell are loaded PCP_KNN_BATCH (or 2 for the wide top-k) at a time before
-// they are pushed, so the loads of a batch are in flight together instead of one dependent
-// round trip per candidate.  Push order is unchanged (and irrelevant: (d2, j) order).
-#ifndef PCP_KNN_BATCH
-#define PCP_KNN_BATCH 4
-#endif
-#ifndef PCP_T_MX  // tiled normals: keys kept per lane beyond k (the re-rank's slack)
-#define PCP_T_MX 1
-#endif
-#ifndef PCP_T_SB  // staged points per lane per load batch (tiled normals)
-#define PCP_T_SB 4
-#endif
-#ifndef PCP_T_RB  // fp64 records per gather batch of the tiled normals' re-rank and PCA
-#define PCP_T_RB 8
-#endif
 #ifndef PCP_T_WB  // window rows per batch of cell-start loads (tiled normals)
 #define PCP_T_WB 5
 #endif
-#ifndef PCP_T_NOPCA  // profiling builds only: the tile skips its mean/covariance passes (planes wrong)
-#define PCP_T_NOPCA 0
-#endif
+// K3: batch nearestKSearch, the near pass (cell rings only; k_knn_coop takes the deferred rows).
+// Rows ascending by (d2, internal j), indices mapped through index_mapping_ (kd_tree.h:837-842);
+// entries past min(k, size) are -1 / +inf.
 template <int K>
-struct KnnVisitor {
-    static constexpr int U = K <= 16 ? PCP_KNN_BATCH : 2;
-    const double4* pts;
-    double qx, qy, qz;
-    TopK<K> top;
-    // a known upper bound on the query's k-th d2 (the tile's: k points it already holds), or inf
-    double cap = INFINITY;
-    // pruning radius^2 (1e-12 covers the rounding of the cell-box bound and of d2)
-    __device__ double bound() const { return fmin(top.kth(), cap) * (1.0 + 1e-12); }
-    __device__ __forceinline__ void take(double d, int j) {
-        if (d <= cap * (1.0 + 1e-12)) top.push(d, j);
-    }
-    __device__ void visit(uint32_t s, uint32_t e) {
-        uint32_t t = s;
-        for (; t + U <= e; t += U) {
-            double4 p[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) p[u] = pts[t + u];
-#pragma unroll
-            for (int u = 0; u < U; u++) take(l2_simple(qx, qy, qz, p[u]), (int)p[u].w);
-        }
-        for (; t < e; t++) {
-            const double4 p = pts[t];
-            take(l2_simple(qx, qy, qz, p), (int)p.w);
-        }
-    }
-};
-
-__device__ __forceinline__ const double* qptr(const double* q, size_t stride, int64_t i) {
-    return (const double*)((const char*)q + (size_t)i * stride);
-}
-
-// Two-pass scheduling of the ring search (grid.hpp): the near pass (FAR = false) runs the
-// cell rings only and appends queries whose bound reaches past them to `far_list`; the far
-// pass (FAR = true) re-runs exactly those (or every query when far_list is null) with the
-// brick-level search.  Keeps the common path's register footprint small.
-struct FarList {
-    int32_t* list;
-    uint32_t* count;
-    // optional, per entry: an upper bound on the query's exact k-th d2 (the k-th exact d2 of a
-    // set of k points the earlier pass already holds), so the next pass prunes from the start
-    double* ub = nullptr;
-};
-
-// Deferred queries are few but each is expensive, so the far pass gives every one its own
-// wave (lane 0) to spread them over all CUs instead of packing them into a few waves.
-template <bool FAR>
-__device__ __forceinline__ int64_t work_count(const FarList& f, int64_t n) {
-    if (FAR && f.list) return (threadIdx.x & 63) ? 0 : (int64_t)*f.count * 64;
-    return n;
-}
-template <bool FAR>
-__device__ __forceinline__ int64_t work_item(const FarList& f, int64_t w) {
-    return (FAR && f.list) ? (int64_t)f.list[w >> 6] : w;
-}
-__device__ __forceinline__ void defer(const FarList& f, int64_t i, double ub = INFINITY) {
-    const uint32_t at = atomicAdd(f.count, 1u);
-    f.list[at] = (int32_t)i;
-    if (f.ub) f.ub[at] = ub;
-}
-
-// K3: batch nearestKSearch.  Rows ascending by (d2, internal j), indices mapped through
-// index_mapping_ (kd_tree.h:837-842); entries past min(k, size) are -1 / +inf.
-template <int K, bool FAR>
 __global__ __launch_bounds__(kB) void k_knn(GridDesc g, const double4* pts, const int32_t* mapping, int identity,
                                             const double* q, size_t qstride, int64_t nq, int k, int kk,
                                             double mc, int32_t* oidx, double* od2, FarList far) {
-    const int64_t nw = work_count<FAR>(far, nq);
-    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = work_item<FAR>(far, w);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nq; i += (int64_t)gridDim.x * blockDim.x) {
         const double* qp = qptr(q, qstride, i);
         KnnVisitor<K> v;
         v.pts = pts;
         v.qx = qp[0]; v.qy = qp[1]; v.qz = qp[2];
         v.top.init(kk);
         if (kk > 0 && finite3(v.qx, v.qy, v.qz) &&
-            !ring_search<double, KnnVisitor<K>, FAR>(g, v.qx, v.qy, v.qz, mc, v)) {
+            !ring_search<double, KnnVisitor<K>, false>(g, v.qx, v.qy, v.qz, mc, v)) {
             defer(far, i);
             continue;
         }
@@ -148,386 +58,6 @@ __global__ __launch_bounds__(kB) void k_knn(GridDesc g, const double4* pts, cons
             ri[r] = -1;
             if (od2) rd[r] = INFINITY;
         }
-    }
-}
-
-// ---- the far pass, wave-cooperative: one query per wave.  The deferred queries are the few
-// whose k-th neighbour lies beyond the near pass's cell rings -- isolated points, where one lane
-// walking rings of bricks alone took milliseconds.  Here the cells of each Chebyshev ring (then
-// the bricks of each brick ring) are dealt round-robin over the 64 lanes; every lane keeps its
-// own exact top-k of what it scanned, pruned by min(own k-th, the wave's shared bound), where
-// the shared bound -- the minimum over lanes of their k-th -- is an upper bound on the global
-// k-th (a superset has a smaller k-th), refreshed at each ring.  Every point within the final
-// global k-th distance was scanned by some lane, so merging the lanes' lists (k rounds of a
-// wave-wide lexicographic argmin) gives the exact FLANN (d2, j) order.
-template <int K>
-struct CoopVisitor {
-    const double4* pts;
-    double qx, qy, qz;
-    double shared = INFINITY;  // wave-uniform
-    TopK<K> top;
-    __device__ double bound() const { return fmin(top.kth(), shared) * (1.0 + 1e-12); }
-    __device__ double ubound() const { return shared * (1.0 + 1e-12); }
-    // a point beyond the wave's shared bound (an upper bound on the global k-th) cannot be in
-    // the result: only the cheap compare, not the K-slot insertion (which a lane's own list,
-    // empty until it has seen k points, would otherwise take for every point)
-    __device__ __forceinline__ void take(double d, int j) {
-        if (d <= shared * (1.0 + 1e-12)) top.push(d, j);
-    }
-};
-// An upper bound on the wave's exact k-th d2 within 2^-20 of it, without copying the lists:
-// the smallest tau (a double whose low word is all ones) with at least kk list entries <= tau,
-// by bisection on tau's high word; each step counts the entries with one compare per slot into
-// a lane mask and popcounts (SALU), no cross-lane moves.  +inf when fewer than kk are finite.
-template <int K>
-__device__ double kth_bound(const TopK<K>& top, int kk) {
-    auto count = [&](double t) {
-        int c = 0;
-#pragma unroll
-        for (int i = 0; i < K; i++) c += __popcll(__ballot(i < kk && top.d[i] <= t));
-        return c;
-    };
-    if (count(DBL_MAX) < kk) return INFINITY;
-    uint32_t lo = 0, hi = 0x7fefffffu;  // DBL_MAX's high word
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (count(__hiloint2double((int)mid, (int)0xffffffffu)) >= kk) hi = mid;
-        else lo = mid + 1;
-    }
-    return __hiloint2double((int)hi, (int)0xffffffffu);
-}
-
-// An upper bound on the wave's exact k-th d2, cheap enough to refresh inside a shell: the
-// kk-th smallest of the lanes' own best d2 (a subset of the union, so its kk-th smallest is at
-// least the union's), by a 64-lane bitonic sort; +inf until kk lanes hold a point.
-template <int K>
-__device__ double wave_kth_of_bests(const TopK<K>& top, int kk, int lane) {
-    double x = INFINITY;
-#pragma unroll
-    for (int i = 0; i < K; i++)
-        if (i == kk - 1) x = top.d[i];
-#pragma unroll
-    for (int k2 = 2; k2 <= 64; k2 <<= 1)
-#pragma unroll
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            const double y = __shfl_xor(x, j, 64);
-            const bool up = (lane & k2) == 0, lower = (lane & j) == 0;
-            x = (lower == up) ? fmin(x, y) : fmax(x, y);
-        }
-    return __shfl(x, kk - 1, 64);
-}
-
-// bricks per lane per batch of the far pass's shells (8 spilled the K = 32 lists to scratch:
-// ~700 bytes per lane, every list update a round trip to memory)
-constexpr int kCoopBB = 4;
-
-template <int K>
-__device__ void coop_search(const GridDesc& g, double mc, CoopVisitor<K>& v, int lane, int kk,
-                            int* shells = nullptr, long long* tk = nullptr) {
-    const double fx = cell_f<double>(g, v.qx, 0), fy = cell_f<double>(g, v.qy, 1), fz = cell_f<double>(g, v.qz, 2);
-    const int cx = (int)floor(fx), cy = (int)floor(fy), cz = (int)floor(fz);
-    const double lx = fx - cx, ly = fy - cy, lz = fz - cz;
-    const double h2 = g.h * g.h;
-    const double dmin = fmin(fmin(fmin(lx, 1 - lx), fmin(ly, 1 - ly)), fmin(lz, 1 - lz));
-    int far = 0;
-    far = max(far, max(cx - (g.n[0] - 1), -cx));
-    far = max(far, max(cy - (g.n[1] - 1), -cy));
-    far = max(far, max(cz - (g.n[2] - 1), -cz));
-    const int rmax = far + max(g.n[0], max(g.n[1], g.n[2]));
-    const int smax = min(rmax, kCellRings);
-    // Point ranges gathered one per lane (a cell, or a row's one or two runs), then their points
-    // dealt flat over the lanes -- point p to lane p % 64, its range found by a binary search of
-    // the ranges' prefix in LDS -- so no lane runs a long range as a serial chain of loads while
-    // the others wait.  Wave-uniform call.
-    __shared__ uint32_t s_fr[kB / 64][4][64];  // per wave: the ranges' prefix, starts, lengths
-    uint32_t* const f_pre = s_fr[threadIdx.x >> 6][0];
-    uint32_t* const f_s1 = s_fr[threadIdx.x >> 6][1];
-    uint32_t* const f_l1 = s_fr[threadIdx.x >> 6][2];
-    uint32_t* const f_s2 = s_fr[threadIdx.x >> 6][3];
-    constexpr int kFlatU = 2;  // points per lane in flight (4 spilled the K = 32 lists to scratch)
-    auto flat_visit = [&](uint32_t s1, uint32_t l1, uint32_t s2, uint32_t l2) {
-        const uint32_t cnt = l1 + l2;
-        uint32_t inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t tv = (uint32_t)__shfl_up((int)inc, o, 64);
-            if (lane >= o) inc += tv;
-        }
-        const uint32_t tot = (uint32_t)__shfl((int)inc, 63, 64);
-        if (tot == 0) return;
-        f_pre[lane] = inc - cnt;
-        f_s1[lane] = s1;
-        f_l1[lane] = l1;
-        f_s2[lane] = s2;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (uint32_t p0 = 0; p0 < tot; p0 += 64u * kFlatU) {  // wave-uniform
-            uint32_t idx[kFlatU];
-#pragma unroll
-            for (int u = 0; u < kFlatU; u++) {
-                const uint32_t pp = p0 + (uint32_t)lane + 64u * u;
-                // the owner: the last lane whose prefix is <= pp (an empty lane shares its prefix
-                // with the next, so the last one is the non-empty owner)
-                int o = 0;
-#pragma unroll
-                for (int b = 32; b >= 1; b >>= 1) o += f_pre[o + b] <= pp ? b : 0;
-                const uint32_t off = pp - f_pre[o], a1 = f_l1[o];
-                idx[u] = pp < tot ? (off < a1 ? f_s1[o] + off : f_s2[o] + (off - a1)) : ~0u;
-            }
-            double4 q4[kFlatU];
-#pragma unroll
-            for (int u = 0; u < kFlatU; u++) q4[u] = v.pts[idx[u] != ~0u ? idx[u] : 0u];
-#pragma unroll
-            for (int u = 0; u < kFlatU; u++)
-                if (idx[u] != ~0u) v.take(l2_simple(v.qx, v.qy, v.qz, q4[u]), (int)q4[u].w);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next call rewrites f_*
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    uint32_t t = 0;  // the wave's cell / brick counter: item t belongs to lane t % 64
-    uint32_t rs = 0, rl = 0;  // this lane's pending cell range (flushed every 64 items)
-    for (int s = 0; s <= smax + 1; s++) {
-        if (s > 0) {
-            v.shared = fmin(v.shared, kth_bound<K>(v.top, kk));
-            const double rmin = (double)(s - 1) + dmin - mc;
-            if (rmin > 0 && rmin * rmin * h2 > v.ubound()) return;
-        }
-        if (s > smax) break;
-        const int z0 = max(cz - s, 0), z1 = min(cz + s, g.n[2] - 1);
-        const int y0 = max(cy - s, 0), y1 = min(cy + s, g.n[1] - 1);
-        const int x0 = max(cx - s, 0), x1 = min(cx + s, g.n[0] - 1);
-        if (z0 > z1 || y0 > y1 || x0 > x1) continue;
-        for (int z = z0; z <= z1; z++) {
-            const bool zface = (z == cz - s) || (z == cz + s);
-            const double gz2 = sq_gap(axis_gap<double>(z, cz, lz), mc);
-            if (gz2 * h2 > v.ubound()) continue;
-            for (int y = y0; y <= y1; y++) {
-                const bool yface = zface || (y == cy - s) || (y == cy + s);
-                const double gyz2 = gz2 + sq_gap(axis_gap<double>(y, cy, ly), mc);
-                if (gyz2 * h2 > v.ubound()) continue;
-                const int step = yface ? 1 : 2 * s;
-                for (int x = yface ? x0 : cx - s; x <= x1; x += (step > 0 ? step : 1)) {
-                    if (x < x0) continue;
-                    const bool mine = (t & 63u) == (uint32_t)lane;
-                    t++;
-                    if (mine && (gyz2 + sq_gap(axis_gap<double>(x, cx, lx), mc)) * h2 <= v.bound()) {
-                        uint32_t st, en;
-                        if (cell_range(g, x, y, z, st, en)) {
-                            rs = st;
-                            rl = en - st;
-                        }
-                    }
-                    if ((t & 63u) == 0u) {  // (uniform) a chunk of 64 cells: its points, flat
-                        flat_visit(rs, rl, 0u, 0u);
-                        rl = 0u;
-                    }
-                }
-            }
-        }
-        flat_visit(rs, rl, 0u, 0u);  // the ring's last partial chunk
-        rl = 0u;
-    }
-    if (rmax <= kCellRings) return;
-    // bricks of 4x4x4 cells, rings outward, the cells phase 1 covered skipped
-    const int bx = cx >> 2, by = cy >> 2, bz = cz >> 2;
-    const double ox = fx - 4 * bx, oy = fy - 4 * by, oz = fz - 4 * bz;
-    const double bdmin = fmin(fmin(fmin(ox, 4 - ox), fmin(oy, 4 - oy)), fmin(oz, 4 - oz));
-    int farb = 0;
-    farb = max(farb, max(bx - (g.nb[0] - 1), -bx));
-    farb = max(farb, max(by - (g.nb[1] - 1), -by));
-    farb = max(farb, max(bz - (g.nb[2] - 1), -bz));
-    const int sbmax = farb + max(g.nb[0], max(g.nb[1], g.nb[2]));
-    __shared__ int4 s_flat[kB / 64][64 * kCoopBB];  // per wave: a batch's occupied bricks {x, y, z, word}
-    __shared__ uint16_t s_rows[kB / 64][64 * kCoopBB * 16];  // per wave: their non-empty rows (brick << 4 | row)
-    int4* const flat = s_flat[threadIdx.x >> 6];
-    uint16_t* const rows = s_rows[threadIdx.x >> 6];
-    // rings closer than `farb` lie wholly outside the grid (a query far away from it)
-    if (tk) tk[0] = clock64();
-    for (int sb = farb; sb <= sbmax; sb++) {
-        if (shells) (*shells)++;
-        const long long c0 = tk ? (long long)clock64() : 0;
-        v.shared = fmin(v.shared, kth_bound<K>(v.top, kk));
-        if (tk) tk[1] += (long long)clock64() - c0;
-        if (sb > 0) {
-            const double rmin = (double)(4 * (sb - 1)) + bdmin - mc;
-            if (rmin > 0 && rmin * rmin * h2 > v.ubound()) return;
-        }
-        // the shell's bricks inside the grid: two z-faces, two y-faces (z strictly inside), two
-        // x-faces (y and z strictly inside), each a rectangle clipped to the grid; brick t of the
-        // shell goes to lane t % 64
-        const int X0 = max(bx - sb, 0), X1 = min(bx + sb, g.nb[0] - 1);
-        const int Y0 = max(by - sb, 0), Y1 = min(by + sb, g.nb[1] - 1);
-        const int Z0 = max(bz - sb, 0), Z1 = min(bz + sb, g.nb[2] - 1);
-        if (X0 > X1 || Y0 > Y1 || Z0 > Z1) continue;
-        const int Yi0 = max(by - sb + 1, 0), Yi1 = min(by + sb - 1, g.nb[1] - 1);
-        const int Zi0 = max(bz - sb + 1, 0), Zi1 = min(bz + sb - 1, g.nb[2] - 1);
-        int64_t area[6];
-        int fixc[6];
-        const int nx = X1 - X0 + 1, ny = Y1 - Y0 + 1, nyi = max(Yi1 - Yi0 + 1, 0), nzi = max(Zi1 - Zi0 + 1, 0);
-        for (int f = 0; f < 6; f++) {
-            const int sgn = (f & 1) ? 1 : -1;
-            if (f < 2) {  // z = bz -+ sb
-                fixc[f] = bz + sgn * sb;
-                area[f] = (fixc[f] >= 0 && fixc[f] < g.nb[2] && (sb > 0 || f == 0)) ? (int64_t)nx * ny : 0;
-            } else if (f < 4) {  // y = by -+ sb, z inside
-                fixc[f] = by + sgn * sb;
-                area[f] = (sb > 0 && fixc[f] >= 0 && fixc[f] < g.nb[1]) ? (int64_t)nx * nzi : 0;
-            } else {  // x = bx -+ sb, y and z inside
-                fixc[f] = bx + sgn * sb;
-                area[f] = (sb > 0 && fixc[f] >= 0 && fixc[f] < g.nb[0]) ? (int64_t)nyi * nzi : 0;
-            }
-        }
-        const int64_t total = area[0] + area[1] + area[2] + area[3] + area[4] + area[5];
-        // bricks t = lane + 64 u: the occupancy words of a batch are loaded together (mostly
-        // empty bricks around isolated queries: one dependent load each would serialise)
-        constexpr int kBB = kCoopBB;
-        for (int64_t base = 0; base < total; base += 64 * kBB) {  // wave-uniform trip count
-            const long long cb0 = tk ? (long long)clock64() : 0;
-            const int64_t t0 = base + lane;
-            int bxs[kBB], bys[kBB], bzs[kBB];
-            int32_t occ[kBB];
-            uint32_t msk[kBB], bat[kBB];  // row masks and flat[] positions of this lane's bricks
-#pragma unroll
-            for (int u = 0; u < kBB; u++) {
-                const int64_t t = t0 + 64 * u;
-                int xb = 0, yb = 0, zb = 0;
-                bool live = t < total;
-                if (live) {
-                    int f = 0;
-                    int64_t r = t;
-                    while (r >= area[f]) { r -= area[f]; f++; }
-                    if (f < 2) {
-                        xb = X0 + (int)(r % nx); yb = Y0 + (int)(r / nx); zb = fixc[f];
-                    } else if (f < 4) {
-                        xb = X0 + (int)(r % nx); zb = Zi0 + (int)(r / nx); yb = fixc[f];
-                    } else {
-                        yb = Yi0 + (int)(r % nyi); zb = Zi0 + (int)(r / nyi); xb = fixc[f];
-                    }
-                    const double gz = zb < bz ? (oz + 4.0 * (bz - zb - 1)) : (zb > bz ? (4.0 - oz + 4.0 * (zb - bz - 1)) : 0.0);
-                    const double gy = yb < by ? (oy + 4.0 * (by - yb - 1)) : (yb > by ? (4.0 - oy + 4.0 * (yb - by - 1)) : 0.0);
-                    const double gx = xb < bx ? (ox + 4.0 * (bx - xb - 1)) : (xb > bx ? (4.0 - ox + 4.0 * (xb - bx - 1)) : 0.0);
-                    live = (sq_gap(gz, mc) + sq_gap(gy, mc) + sq_gap(gx, mc)) * h2 <= v.bound();
-                }
-                bxs[u] = xb; bys[u] = yb; bzs[u] = zb;
-                occ[u] = live ? g.brick[((int64_t)zb * g.nb[1] + yb) * g.nb[0] + xb] : -1;
-            }
-            const long long cb1 = tk ? (long long)clock64() : 0;
-            if (tk) tk[2] += cb1 - cb0;  // brick coordinates, pruning and occupancy loads
-            // The batch's occupied bricks are listed in LDS, then their rows that hold points
-            // (the brick word's row mask on dense fp64 grids; all 16 rows otherwise) as one flat
-            // item list dealt round-robin over the lanes: every lane's round is one row's
-            // cstart round trip, and empty rows cost none.
-            uint32_t nocc = 0, nrow = 0;
-            uint32_t myrows = 0;
-#pragma unroll
-            for (int u = 0; u < kBB; u++) {
-                const uint64_t m = __ballot(occ[u] >= 0);
-                if (occ[u] >= 0) {
-                    const uint32_t at = nocc + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    flat[at] = make_int4(bxs[u], bys[u], bzs[u], occ[u]);
-                    bat[u] = at;
-                    const uint32_t rm = (g.dense && occ[u] > 0) ? (uint32_t)occ[u] & 0xffffu : 0xffffu;
-                    msk[u] = rm;
-                    myrows += (uint32_t)__popc(rm);
-                } else {
-                    msk[u] = 0u;
-                }
-                nocc += (uint32_t)__popcll(m);
-            }
-            // exclusive scan of the lanes' row counts -> this lane's first row slot
-            uint32_t incl = myrows;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t tv = (uint32_t)__shfl_up((int)incl, o, 64);
-                if (lane >= o) incl += tv;
-            }
-            nrow = (uint32_t)__shfl((int)incl, 63, 64);
-            uint32_t slot = incl - myrows;
-#pragma unroll
-            for (int u = 0; u < kBB; u++) {
-                uint32_t rm = msk[u];
-                while (rm) {
-                    const uint32_t r = (uint32_t)__builtin_ctz(rm);
-                    rm &= rm - 1u;
-                    rows[slot++] = (uint16_t)((bat[u] << 4) | r);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // Rows in chunks of 64, one per lane: the lane resolves its row to at most two point
-            // ranges (one cstart round trip for the whole chunk), then the chunk's points are
-            // dealt flat over the lanes -- point p to lane p % 64, its range found by a binary
-            // search of the ranges' prefix in LDS -- so a long row no longer runs as one lane's
-            // serial chain of loads while the others wait.
-            for (uint32_t r0 = 0; r0 < nrow; r0 += 64) {
-                const uint32_t ir = r0 + (uint32_t)lane;
-                uint32_t s1 = 0, l1 = 0, s2 = 0, l2 = 0;
-                do {
-                    if (ir >= nrow) break;
-                    const uint32_t it = rows[ir];
-                    const int4 bk = flat[it >> 4];
-                    const int y = 4 * bk.y + (int)(it & 3), z = 4 * bk.z + (int)((it >> 2) & 3);
-                    if (y >= g.n[1] || z >= g.n[2]) break;
-                    const double cyz2 = sq_gap(axis_gap<double>(z, cz, lz), mc) + sq_gap(axis_gap<double>(y, cy, ly), mc);
-                    if (cyz2 * h2 > v.bound()) break;
-                    const bool yzin = abs(z - cz) <= kCellRings && abs(y - cy) <= kCellRings;
-                    int xa = 4 * bk.x, xe = min(4 * bk.x + 3, g.n[0] - 1);
-                    while (xa <= xe && (cyz2 + sq_gap(axis_gap<double>(xa, cx, lx), mc)) * h2 > v.bound()) xa++;
-                    while (xe >= xa && (cyz2 + sq_gap(axis_gap<double>(xe, cx, lx), mc)) * h2 > v.bound()) xe--;
-                    if (xa > xe) break;
-                    const int64_t rb = g.dense ? dense_id(g, 0, y, z) : (int64_t)bk.w * 64 + local_of(0, y, z);
-                    auto range = [&](int x0, int x1, uint32_t& st, uint32_t& len) {  // cells [x0, x1]
-                        if (x0 > x1) return;
-                        const int64_t c0 = g.dense ? rb + x0 : rb + (x0 & 3);
-                        st = g.cstart[c0];
-                        len = g.cstart[c0 + (x1 - x0) + 1] - st;
-                    };
-                    if (yzin) {
-                        range(xa, min(xe, cx - kCellRings - 1), s1, l1);
-                        range(max(xa, cx + kCellRings + 1), xe, s2, l2);
-                    } else {
-                        range(xa, xe, s1, l1);
-                    }
-                } while (false);
-                flat_visit(s1, l1, s2, l2);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next batch rewrites flat[]
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const long long cb2 = tk ? (long long)clock64() : 0;
-            if (tk) tk[3] += cb2 - cb1;  // the occupied bricks' rows and points
-            // tighten the shared bound mid-shell (the exact k-th is refreshed per shell)
-            if (kk <= 64) v.shared = fmin(v.shared, wave_kth_of_bests<K>(v.top, kk, lane));
-            if (tk) tk[4] += (long long)clock64() - cb2;
-        }
-    }
-}
-
-// merge the lanes' top-k lists: round r leaves the r-th (d2, j) of the query in lane r's
-// (md, mj) (r < kk); every lane must call it
-template <int K>
-__device__ __forceinline__ void coop_merge(CoopVisitor<K>& v, int kk, int lane, double& md, int& mj) {
-    v.top.normalize(kk);
-    md = INFINITY;
-    mj = INT_MAX;
-    for (int r = 0; r < kk; r++) {
-        double bd = v.top.best_d();
-        int bj = v.top.best_j(), bl = lane;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double od = __shfl_xor(bd, o, 64);
-            const int oj = __shfl_xor(bj, o, 64), ol = __shfl_xor(bl, o, 64);
-            const bool take = lex_less(od, oj, bd, bj);
-            bd = take ? od : bd;
-            bj = take ? oj : bj;
-            bl = take ? ol : bl;
-        }
-        if (lane == bl && bj != INT_MAX) v.top.pop_best();
-        if (lane == r) { md = bd; mj = bj; }
     }
 }
 
@@ -562,7 +92,7 @@ template <int K>
 __global__ __launch_bounds__(kB, 2) void k_normals_coop(GridDesc g, const double4* pts, const int32_t* mapping,
                                                      int identity, const int32_t* pos_of_j, int kk, double mc,
                                                      pcp_plane* out, int64_t n_out, FarList far,
-                                                     unsigned long long* dbg = nullptr) {
+                                                     unsigned long long* dbg) {
     const int lane = threadIdx.x & 63;
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x / 64), cnt = *far.count;
     for (int64_t w = blockIdx.x * (int64_t)(blockDim.x / 64) + (threadIdx.x >> 6); w < cnt; w += nwaves) {
@@ -573,11 +103,12 @@ __global__ __launch_bounds__(kB, 2) void k_normals_coop(GridDesc g, const double
         v.qx = qp.x; v.qy = qp.y; v.qz = qp.z;
         v.top.init(kk);
         if (far.ub) v.shared = far.ub[w];  // the earlier passes' k-th: pruning from the first ring
+        // dbg: null, or 16 counters of the profiling build (PCP_NORMALS_STATS)
         int shells = 0;
         const long long t0 = dbg ? (long long)clock64() : 0;
         long long tk[5] = {t0, 0, 0, 0, 0};
         coop_search<K>(g, mc, v, lane, kk, dbg ? &shells : nullptr, dbg ? tk : nullptr);
-        if (dbg && lane == 0) {  // PCP_KNN_DEBUG: shells walked and cycles per deferred query
+        if (dbg && lane == 0) {  // shells walked and cycles per deferred query
             const unsigned long long dt = (unsigned long long)((long long)clock64() - t0);
             atomicAdd(dbg + 0, 1ull);
             atomicAdd(dbg + 1, (unsigned long long)shells);
@@ -585,7 +116,7 @@ __global__ __launch_bounds__(kB, 2) void k_normals_coop(GridDesc g, const double
             atomicAdd(dbg + 3, dt);
             atomicMax(dbg + 4, dt);
             atomicAdd(dbg + 9, (unsigned long long)(tk[0] - t0));  // ring phase
-            atomicAdd(dbg + 10, (unsigned long long)tk[1]);        // global_kth in the shells
+            atomicAdd(dbg + 10, (unsigned long long)tk[1]);        // kth_bound in the shells
             if (dt >= dbg[4]) {  // the slowest query's coordinates and phases (racy, debugging only)
                 dbg[11] = (unsigned long long)(tk[0] - t0);
                 dbg[12] = (unsigned long long)tk[1];
@@ -630,181 +161,6 @@ __global__ __launch_bounds__(kB, 2) void k_normals_coop(GridDesc g, const double
     }
 }
 
-// K4 count pass: #points with d2 < r2 (strict, FLANN RadiusResultSet), truncated to max_nn
-struct CountVisitor {
-    const double4* pts;
-    double qx, qy, qz, r2, b;
-    uint32_t cnt;
-    __device__ double bound() const { return b; }
-    __device__ void visit(uint32_t s, uint32_t e) {
-        uint32_t t = s;
-        for (; t + 4 <= e; t += 4) {
-            const double4 p0 = pts[t], p1 = pts[t + 1], p2 = pts[t + 2], p3 = pts[t + 3];
-            cnt += (l2_simple(qx, qy, qz, p0) < r2 ? 1u : 0u) + (l2_simple(qx, qy, qz, p1) < r2 ? 1u : 0u) +
-                   (l2_simple(qx, qy, qz, p2) < r2 ? 1u : 0u) + (l2_simple(qx, qy, qz, p3) < r2 ? 1u : 0u);
-        }
-        for (; t < e; t++) cnt += l2_simple(qx, qy, qz, pts[t]) < r2 ? 1u : 0u;
-    }
-};
-
-template <bool FAR>
-__global__ __launch_bounds__(kB) void k_radius_count(GridDesc g, const double4* pts, const double* q, size_t qstride,
-                                                     int64_t nq, double r2, uint32_t cap, double mc, int32_t* ocnt,
-                                                     FarList far) {
-    const int64_t nw = work_count<FAR>(far, nq);
-    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = work_item<FAR>(far, w);
-        const double* qp = qptr(q, qstride, i);
-        CountVisitor v{pts, qp[0], qp[1], qp[2], r2, r2 * (1.0 + 1e-12), 0u};
-        if (finite3(v.qx, v.qy, v.qz) && !ring_search<double, CountVisitor, FAR>(g, v.qx, v.qy, v.qz, mc, v)) {
-            defer(far, i);
-            continue;
-        }
-        ocnt[i] = (int32_t)(v.cnt < cap ? v.cnt : cap);
-    }
-}
-
-// K4 fill pass.  A row that max_nn does not truncate (m < cap) receives its points in
-// visiting order (k_sort_rows orders it afterwards); a possibly truncated row (m == cap)
-// keeps the m best found so far sorted by (d2, j) by insertion.
-struct FillVisitor {
-    const double4* pts;
-    double qx, qy, qz, r2, b;
-    int32_t* ri;
-    double* rd;
-    int64_t m, filled;
-    bool append;
-    __device__ double bound() const { return b; }
-    __device__ void visit(uint32_t s, uint32_t e) {
-        if (append) {  // batched loads; entries appended in visiting order
-            uint32_t t = s;
-            for (; t + 4 <= e; t += 4) {
-                double4 p[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) p[u] = pts[t + u];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const double d = l2_simple(qx, qy, qz, p[u]);
-                    if (d < r2 && filled < m) { rd[filled] = d; ri[filled] = (int)p[u].w; filled++; }
-                }
-            }
-            for (; t < e; t++) {
-                const double4 p = pts[t];
-                const double d = l2_simple(qx, qy, qz, p);
-                if (d < r2 && filled < m) { rd[filled] = d; ri[filled] = (int)p.w; filled++; }
-            }
-            return;
-        }
-        for (uint32_t t = s; t < e; t++) {
-            const double4 p = pts[t];
-            const double d = l2_simple(qx, qy, qz, p);
-            if (!(d < r2)) continue;
-            const int j = (int)p.w;
-            int64_t pos;
-            if (filled < m) pos = filled++;
-            else if (lex_less(d, j, rd[m - 1], ri[m - 1])) pos = m - 1;
-            else continue;
-            while (pos > 0 && lex_less(d, j, rd[pos - 1], ri[pos - 1])) {
-                rd[pos] = rd[pos - 1];
-                ri[pos] = ri[pos - 1];
-                pos--;
-            }
-            rd[pos] = d;
-            ri[pos] = j;
-        }
-    }
-};
-
-// Orders each appended CSR row by (d2, j) and maps j -> caller index.  One wave per row:
-// rows up to kSortMax elements are bitonic-sorted in the wave's LDS slice; longer rows
-// (rare) are insertion-sorted by lane 0 in place.
-constexpr int kSortMax = 1024;
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__global__ __launch_bounds__(256) void k_sort_rows(const int64_t* off, int64_t nq, uint32_t cap, int32_t* ri,
-                                                   double* rd, const int32_t* mapping, int identity) {
-    __shared__ double sd[4][kSortMax];
-    __shared__ int sj[4][kSortMax];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + w; row < nq; row += nw) {
-        const int64_t o = off[row], m = off[row + 1] - o;
-        if (m <= 0 || (uint64_t)m >= cap) {  // empty, or an insertion-sorted (truncatable) row
-            if (!identity)
-                for (int64_t t = lane; t < m; t += 64) ri[o + t] = mapping[ri[o + t]];
-            continue;
-        }
-        if (m > kSortMax) {
-            if (lane == 0) {
-                for (int64_t a = 1; a < m; a++) {
-                    const double d = rd[o + a];
-                    const int j = ri[o + a];
-                    int64_t p = a;
-                    while (p > 0 && lex_less(d, j, rd[o + p - 1], ri[o + p - 1])) {
-                        rd[o + p] = rd[o + p - 1];
-                        ri[o + p] = ri[o + p - 1];
-                        p--;
-                    }
-                    rd[o + p] = d;
-                    ri[o + p] = j;
-                }
-            }
-            wave_lds_sync();
-            if (!identity)
-                for (int64_t t = lane; t < m; t += 64) ri[o + t] = mapping[ri[o + t]];
-            continue;
-        }
-        int N = 1;
-        while (N < m) N <<= 1;
-        for (int t = lane; t < N; t += 64) {
-            sd[w][t] = t < m ? rd[o + t] : INFINITY;
-            sj[w][t] = t < m ? ri[o + t] : INT_MAX;
-        }
-        wave_lds_sync();
-        for (int k = 2; k <= N; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = lane; t < N; t += 64) {
-                    const int u = t ^ j;
-                    if (u > t) {
-                        const double a = sd[w][t], b = sd[w][u];
-                        const int ja = sj[w][t], jb = sj[w][u];
-                        const bool up = (t & k) == 0;
-                        if (up == lex_less(b, jb, a, ja)) {
-                            sd[w][t] = b; sd[w][u] = a;
-                            sj[w][t] = jb; sj[w][u] = ja;
-                        }
-                    }
-                }
-                wave_lds_sync();
-            }
-        for (int t = lane; t < m; t += 64) {
-            rd[o + t] = sd[w][t];
-            ri[o + t] = identity ? sj[w][t] : mapping[sj[w][t]];
-        }
-        wave_lds_sync();
-    }
-}
-
-template <bool FAR>
-__global__ __launch_bounds__(kB) void k_radius_fill(GridDesc g, const double4* pts, const double* q, size_t qstride,
-                                                    int64_t nq, double r2, uint32_t cap, double mc,
-                                                    const int64_t* off, int32_t* oidx, double* od2, FarList far) {
-    const int64_t nw = work_count<FAR>(far, nq);
-    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = work_item<FAR>(far, w);
-        const int64_t o = off[i], m = off[i + 1] - o;
-        if (m <= 0) continue;
-        const double* qp = qptr(q, qstride, i);
-        FillVisitor v{pts, qp[0], qp[1], qp[2], r2, r2 * (1.0 + 1e-12), oidx + o, od2 + o, m, 0,
-                      (uint64_t)m < cap};
-        if (!ring_search<double, FillVisitor, FAR>(g, v.qx, v.qy, v.qz, mc, v))
-            defer(far, i);  // the far pass rebuilds the row from scratch
-    }
-}
-
 // F1 PCA core (eigen_sym3, plane_from_cov): pca.hpp
 
 __global__ void k_plane_default(pcp_plane* out, int64_t n) {
@@ -819,19 +175,20 @@ __global__ void k_keep_deferred(const uint32_t* a, const uint32_t* b, uint32_t* 
     out[1] = b ? *b : 0u;
 }
 
+// The near pass of the normals (k_normals_coop takes the deferred rows).
 // queries = the indexed points themselves, walked in the index's spatial order
-// `in` (near pass only): the sorted positions to process (the tiled kernel's uncertified
-// queries), or every point when in.list is null
+// `in`: the sorted positions to process (the tiled kernel's uncertified queries), or every
+// point when in.list is null
 // ROWS (the near pass over the tiled kernel's uncertified queries): the row walk below; its
 // own instantiation, so the all-points ring path does not carry its registers
-template <int K, bool FAR, bool ROWS = false>
+template <int K, bool ROWS = false>
 __global__ __launch_bounds__(kB) void k_normals(GridDesc g, const double4* pts, const int32_t* mapping, int identity,
                                                 const int32_t* pos_of_j, int64_t n, int kk, double mc,
                                                 pcp_plane* out, int64_t n_out, FarList far,
                                                 FarList in = FarList{nullptr, nullptr}) {
-    const int64_t nw = (!FAR && in.list) ? (int64_t)*in.count : work_count<FAR>(far, n);
+    const int64_t nw = in.list ? (int64_t)*in.count : n;
     for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t s = (!FAR && in.list) ? (int64_t)in.list[w] : work_item<FAR>(far, w);
+        const int64_t s = in.list ? (int64_t)in.list[w] : w;
         const double4 qp = pts[s];
         KnnVisitor<K> v;
         v.pts = pts;
@@ -839,40 +196,31 @@ __global__ __launch_bounds__(kB) void k_normals(GridDesc g, const double4* pts, 
         v.top.init(kk);
         // the tile's k-th: its kk points lie within its window (+-2 cells), inside this pass's
         // window, so the walk below still finds kk points under the cap
-        if (ROWS && !FAR && in.ub) v.cap = in.ub[w];
+        if (ROWS && in.ub) v.cap = in.ub[w];
         // the near pass over the tiled kernel's uncertified queries, on dense grids, walks the
         // window by rows (the queries are indexed points, so they lie inside the grid).  Not for
         // every point: a large k over a dense neighbourhood fills its list faster cell by cell
         // (measured: k = 32 over all 8.86M C3 points 32.7 -> 67.0 ms by rows; the tile's 10.9K
         // uncertified rows 0.3 ms faster, k = 8 0.3 ms)
-        const bool done = (ROWS && !FAR && g.dense)
+        const bool done = (ROWS && g.dense)
                               ? row_window_search<KnnVisitor<K>>(g, v.qx, v.qy, v.qz, mc, v)
-                              : ring_search<double, KnnVisitor<K>, FAR>(g, v.qx, v.qy, v.qz, mc, v);
+                              : ring_search<double, KnnVisitor<K>, false>(g, v.qx, v.qy, v.qz, mc, v);
         if (!done) {
             // the tile's bound or the window's own k-th, whichever is smaller
-            defer(far, s, fmin((!FAR && in.ub) ? in.ub[w] : INFINITY, v.top.kth()));
+            defer(far, s, fmin(in.ub ? in.ub[w] : INFINITY, v.top.kth()));
             continue;
         }
         const int jq = (int)qp.w;
         const int64_t oi = identity ? jq : mapping[jq];
         if (oi >= n_out) continue;
-        // mean, sequential in kNN order (:131-142)
-        double xa = 0, ya = 0, za = 0;
-        v.top.for_each_ascending(kk, [&](int, double, int j) {
-            const double4 p = pts[pos_of_j[j]];
-            xa += p.x; ya += p.y; za += p.z;
-        });
-        xa /= kk; ya /= kk; za /= kk;
-        double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-        v.top.for_each_ascending(kk, [&](int, double, int j) {
-            const double4 p = pts[pos_of_j[j]];
-            const double x0 = p.x - xa, x1 = p.y - ya, x2 = p.z - za;
-            c00 += x0 * x0; c01 += x0 * x1; c02 += x0 * x2;
-            c11 += x1 * x1; c12 += x1 * x2; c22 += x2 * x2;
-        });
-        const double C[9] = {c00, c01, c02, c01, c11, c12, c02, c12, c22};
+        // mean and X X^T, sequential in kNN order (:131-164)
         pcp_plane pl;
-        plane_from_cov(C, xa, ya, za, pl);
+        plane_from_sequence(kk, [&](auto use) {
+            v.top.for_each_ascending(kk, [&](int, double, int j) {
+                const double4 p = pts[pos_of_j[j]];
+                use(p.x, p.y, p.z);
+            });
+        }, pl);
         out[oi] = pl;
     }
 }
@@ -881,19 +229,20 @@ __global__ __launch_bounds__(kB) void k_normals(GridDesc g, const double4* pts, 
 // The wave copies the union of its queries' neighbourhoods -- the box of their cells grown by
 // R cells, one contiguous point run per (y, z) row -- into LDS as fp32 coordinates relative to
 // the box corner plus the sorted position.  Every lane then scans the whole list (uniform trip
-// count, broadcast LDS reads, no divergence) keeping its M = K + PCP_T_MX (1) smallest packed keys
+// count, broadcast LDS reads, no divergence) keeping its M = K + kTileSlack (1) smallest packed keys
 // (bits(fp32 d2) & ~1023 | list index) and the (M+1)-th as a bound with a v_med3_u32 network
 // (M + 1 VALU ops per candidate instead of the fp64 register top-k's divergent shifts).  The
 // kept candidates are re-ranked by the exact FLANN fp64 (d2, j) and sorted; the lane's result
 // is certified when its k-th exact d2 lies strictly below both the bound on every uncached
 // list point (the (M+1)-th key less the fp32 error) and the squared distance to the box faces
-// (points outside the box).  Uncertified lanes go to the exact two-level search (the far pass
-// of k_normals), so the output is that of the exact path bit for bit.
+// (points outside the box).  Uncertified lanes go to the exact two-level search (k_normals'
+// row walk, then k_normals_coop), so the output is that of the exact path bit for bit.
 constexpr int kTileCap = 2048;   // union points per wave (11-bit list index)
 constexpr int kTileRows = 255;   // (y, z) rows per wave (255: the wave's LDS fits 8 waves per CU)
 constexpr int kTileQ = 16383;    // 14-bit fixed-point coordinates: squared distances fit in int32
 constexpr int kTileExt = 96;     // box extent (cells) cap: keeps the fixed-point step fine
 constexpr int kLaneR = 2;        // largest window half-width of the per-lane window scan
+constexpr int kTileSlack = 1;    // keys kept per lane beyond k (the re-rank's slack; 2-4 slower, 0 defers 10x the rows)
 // (dy, dz) of row i of a 5 x 5 (y, z) window, rows by squared distance (the first 9 are the 3 x 3
 // window): (dy + 2) | (dz + 2) << 3 in 6-bit fields, 10 to a word (i is wave-uniform: scalar ops)
 __device__ __forceinline__ void window_row(int i, int& dy, int& dz) {
@@ -925,11 +274,6 @@ __device__ __forceinline__ int wmax_i(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
-}
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // keeps a loaded value live on every lane: a load whose result is only used under a per-lane
 // condition is otherwise sunk into a branch with its own wait, one round trip per load
@@ -1039,7 +383,7 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
                                                      int identity, int64_t n, int kk, int R, double mc,
                                                      pcp_plane* out, int64_t n_out, FarList far,
                                                      unsigned long long* stats, const uint32_t* order) {
-    constexpr int M = K + PCP_T_MX;
+    constexpr int M = K + kTileSlack;
     constexpr uint32_t kMax = 0xffffffffu;
     __shared__ uint2 s_u[kTileCap];
     __shared__ uint32_t s_rs[kTileRows], s_rb[kTileRows + 1];
@@ -1122,7 +466,7 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
             // their rows first, then kSB unconditional loads (a lane past the list reads position
             // 0), so a step waits on one round trip, not kSB
             int rw = 0;
-            constexpr int kSB = PCP_T_SB;
+            constexpr int kSB = 4;  // staged points per lane per load batch (8: neutral)
             for (uint32_t e0 = lane; e0 < total; e0 += 64 * kSB) {
                 uint32_t pi[kSB];
 #pragma unroll
@@ -1309,7 +653,7 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
             // batches of kRB unconditional loads (a slot without a candidate reads position 0 and
             // is discarded), so a wave waits on M / kRB round trips instead of one per candidate
             // (a load under a per-lane condition is a branch with its own wait).
-            constexpr int kRB = PCP_T_RB;
+            constexpr int kRB = 8;  // fp64 records per gather batch of the re-rank and PCA (16: slower)
             double D[M];
             uint32_t P[M];
 #pragma unroll
@@ -1380,14 +724,6 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
             const int jq = (int)q.w;
             const int64_t oi = identity ? jq : mapping[jq];
             if (oi >= n_out) continue;
-#if PCP_T_NOPCA
-            {
-                pcp_plane pl{};
-                pl.normal_x = (float)D[0]; pl.normal_y = (float)D[1]; pl.distance = (float)P[K - 1];
-                out[oi] = pl;
-                continue;
-            }
-#endif
             // mean, sequential in kNN order (calculate_feature.cpp:131-142); the records again in
             // batches of unconditional loads (P[i] is a valid position for every i)
             double xa = 0, ya = 0, za = 0;
@@ -1445,41 +781,6 @@ __global__ __launch_bounds__(64, 2) void k_normals_tile(GridDesc g, const double
     }
 }
 
-// F1 batch: one plane per CSR segment, points xyz[idx[t]] (or xyz[t]) for t in
-// [off[s], off[s+1]), accumulated sequentially in segment order (calculate_feature.cpp:
-// 131-164) -- calculate_plan_parameter_h_points per segment, and the radius variant
-// (calculate_feature.h:15, F4) when the segments are radiusSearch rows.
-__global__ __launch_bounds__(kB) void k_plane_segments(const double* xyz, size_t stride, const int64_t* off,
-                                                       const int32_t* idx, int64_t nseg, pcp_plane* out) {
-    for (int64_t sg = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; sg < nseg;
-         sg += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t s = off[sg], e = off[sg + 1];
-        const int64_t h = e - s;
-        if (h <= 0) {
-            out[sg] = pcp_plane{0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
-            continue;
-        }
-        auto P = [&](int64_t t) { return qptr(xyz, stride, idx ? (int64_t)idx[t] : t); };
-        double xa = 0, ya = 0, za = 0;
-        for (int64_t t = s; t < e; t++) {
-            const double* p = P(t);
-            xa += p[0]; ya += p[1]; za += p[2];
-        }
-        xa /= h; ya /= h; za /= h;
-        double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-        for (int64_t t = s; t < e; t++) {
-            const double* p = P(t);
-            const double x0 = p[0] - xa, x1 = p[1] - ya, x2 = p[2] - za;
-            c00 += x0 * x0; c01 += x0 * x1; c02 += x0 * x2;
-            c11 += x1 * x1; c12 += x1 * x2; c22 += x2 * x2;
-        }
-        const double C[9] = {c00, c01, c02, c01, c11, c12, c02, c12, c22};
-        pcp_plane pl;
-        plane_from_cov(C, xa, ya, za, pl);
-        out[sg] = pl;
-    }
-}
-
 // K7 (main_blend.cpp:306-325): argmin over queries of the 1-NN d2, strict '<' from an
 // initial bound, so the first query wins ties.  Per-block lexicographic (d2, i) minimum.
 __global__ __launch_bounds__(kB) void k_argmin_d2(const double* d2, int64_t n, double* pd, int64_t* pi) {
@@ -1506,139 +807,7 @@ __global__ __launch_bounds__(kB) void k_argmin_d2(const double* d2, int64_t n, d
     }
 }
 
-// ------------------------------------------------------------------ K6: kd_tree_lod
-// fp32 kNN over the float vertices float(p - c) (kd_tree_lod/kd_tree.cpp:39-43, 62-68;
-// the trimesh2 search is external: exact k nearest, ties by vertex index).
-template <int K>
-struct LodVisitor {
-    const float4* pts;
-    float qx, qy, qz;
-    TopK<K, float> top;
-    __device__ float bound() const { return top.kth() * (1.0f + 1e-5f); }
-    __device__ void visit(uint32_t s, uint32_t e) {
-        for (uint32_t t = s; t < e; t++) {
-            const float4 p = pts[t];
-            const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-            float d = dx * dx;
-            d = d + dy * dy;
-            d = d + dz * dz;
-            top.push(d, __float_as_int(p.w));
-        }
-    }
-};
-
-// first original j with point_dis2(k_point, cloud[j]) <= FLT_EPSILON (kd_tree.cpp:91-105)
-struct MatchVisitor {
-    const double4* pts;
-    const int32_t* mapping;
-    int identity;
-    double kx, ky, kz;
-    int best;
-    double bestd;
-    __device__ double bound() const { return (double)FLT_EPSILON * (1.0 + 1e-9); }
-    __device__ void visit(uint32_t s, uint32_t e) {
-        for (uint32_t t = s; t < e; t++) {
-            const double4 p = pts[t];
-            const double dx = kx - p.x, dy = ky - p.y, dz = kz - p.z;
-            double d = dx * dx + dy * dy;  // pow(.,2) + pow(.,2) + pow(.,2)
-            d = d + dz * dz;
-            if (d <= (double)FLT_EPSILON) {
-                const int jo = identity ? (int)p.w : mapping[(int)p.w];
-                if (jo < best) { best = jo; bestd = d; }
-            }
-        }
-    }
-};
-
-template <int K>
-__global__ __launch_bounds__(kB) void k_lod(GridDesc gf, const float4* fpts, GridDesc gd, const double4* dpts,
-                                            const int32_t* dmap, int didentity, const char* cloud, int64_t n,
-                                            const char* q, int64_t nq, int k, int kk, float mcf, double mcd,
-                                            int ci0, int ci1, int ci2, int32_t* oidx, double* od2) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nq; i += (int64_t)gridDim.x * blockDim.x) {
-        const double* qp = (const double*)(q + i * PCP_AOS48_STRIDE);
-        LodVisitor<K> v;
-        v.pts = fpts;
-        v.qx = (float)(qp[0] - ci0); v.qy = (float)(qp[1] - ci1); v.qz = (float)(qp[2] - ci2);
-        v.top.init(kk);
-        ring_search<float>(gf, v.qx, v.qy, v.qz, mcf, v);
-        const double* last = (const double*)(cloud + (n - 1) * PCP_AOS48_STRIDE);
-        v.top.for_each_ascending(kk, [&](int r, float, int jv) {
-            int index = -1;
-            double d2 = INFINITY;
-            if (jv != INT_MAX) {
-                const double* vp = (const double*)(cloud + (int64_t)jv * PCP_AOS48_STRIDE);
-                // vertex float(p - c), neighbour rebuilt as double(float + float(c)) (:71-73)
-                const float fx = (float)(vp[0] - ci0), fy = (float)(vp[1] - ci1), fz = (float)(vp[2] - ci2);
-                MatchVisitor m{dpts, dmap, didentity, (double)(float)(fx + (float)ci0),
-                               (double)(float)(fy + (float)ci1), (double)(float)(fz + (float)ci2), INT_MAX, 0.0};
-                ring_search<double>(gd, m.kx, m.ky, m.kz, mcd, m);
-                if (m.best != INT_MAX) {
-                    index = m.best;
-                    d2 = m.bestd;
-                } else {  // no match: k_dis2 = residual to the last scanned point (:100)
-                    const double dx = m.kx - last[0], dy = m.ky - last[1], dz = m.kz - last[2];
-                    double dd = dx * dx + dy * dy;
-                    d2 = dd + dz * dz;
-                }
-            }
-            oidx[i * k + r] = index;
-            od2[i * k + r] = d2;
-        });
-        for (int r = kk; r < k; r++) {
-            oidx[i * k + r] = -1;
-            od2[i * k + r] = INFINITY;
-        }
-    }
-}
-
-__global__ void k_lod_vertices(const char* cloud, int64_t n, int ci0, int ci1, int ci2, float* v) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double* p = (const double*)(cloud + i * PCP_AOS48_STRIDE);
-        v[3 * i + 0] = (float)(p[0] - ci0);
-        v[3 * i + 1] = (float)(p[1] - ci1);
-        v[3 * i + 2] = (float)(p[2] - ci2);
-    }
-}
-
-int pick_k(int k) {
-    if (k <= 1) return 1;
-    if (k <= 4) return 4;
-    if (k <= 8) return 8;
-    if (k <= 16) return 16;
-    if (k <= 32) return 32;
-    if (k <= 64) return 64;
-    return 0;
-}
-
-unsigned blocks_for(int64_t n) { return grid_for(n, kB, 1 << 22); }
-
-int check_f64_index(pcp_ctx* ctx, const pcp_index* ix) {
-    if (!ctx || !ix) return PCP_ERR_ARG;
-    if (!ix->is_f64) return set_error(ctx, PCP_ERR_ARG, "fp64 (FLANN-contract) index required");
-    return PCP_OK;
-}
-
 }  // namespace
-
-int centroid_aos48_dev(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, double c[4], uint32_t* count);
-
-// deferred-query list of one call (blocks of the call's Tmp)
-struct FarBuf {
-    FarList f{nullptr, nullptr};
-    int alloc(Tmp& tmp, int64_t n, bool with_ub = false) {
-        PCP_TRY(tmp.get(&f.list, n));
-        PCP_TRY(tmp.get(&f.count, 1));
-        if (with_ub) PCP_TRY(tmp.get(&f.ub, n));
-        PCP_HIP(tmp.ctx, hipMemsetAsync(f.count, 0, sizeof(uint32_t), tmp.ctx->stream));
-        return PCP_OK;
-    }
-};
-constexpr unsigned kFarBlocks = 2048;
-
-// a fixed radius that reaches past the near pass's cell rings goes straight to the far pass
-bool radius_needs_far(const pcp_index* ix, double radius) { return radius * ix->g.inv_h >= (double)kCellRings; }
-
 }  // namespace pcp
 
 using namespace pcp;
@@ -1653,8 +822,7 @@ int pcp_knn(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, 
     if (qstride == 0) qstride = 3 * sizeof(double);
     if (nq == 0) return PCP_OK;
     const int kk = (int)(k < ix->n ? k : ix->n);  // kd_tree.h:820-821
-    const int K = pick_k(kk);
-    if (!K) return set_error(ctx, PCP_ERR_UNSUPPORTED, "pcp_knn: k=%d > 64 not supported yet", k);
+    if (kk > 64) return set_error(ctx, PCP_ERR_UNSUPPORTED, "pcp_knn: k=%d > 64 not supported yet", k);
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->knn_far) PCP_HIP(ctx, hipMalloc(&ctx->knn_far, sizeof(uint32_t)));
     const double mc = cell_margin64(ix->g);
@@ -1662,20 +830,13 @@ int pcp_knn(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, 
     Tmp tmp(ctx);
     FarBuf fb;
     PCP_TRY(fb.alloc(tmp, nq));
-#define LAUNCH_KNN(KV)                                                                                          \
-    hipLaunchKernelGGL((k_knn<KV, false>), dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,  \
-                       ix->identity, q, qstride, nq, k, kk, mc, oidx, od2, fb.f);                                  \
-    hipLaunchKernelGGL((k_knn_coop<KV>), dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,         \
-                       ix->identity, q, qstride, k, kk, mc, oidx, od2, fb.f)
-    switch (K) {
-        case 1: LAUNCH_KNN(1); break;
-        case 4: LAUNCH_KNN(4); break;
-        case 8: LAUNCH_KNN(8); break;
-        case 16: LAUNCH_KNN(16); break;
-        case 32: LAUNCH_KNN(32); break;
-        default: LAUNCH_KNN(64); break;
-    }
-#undef LAUNCH_KNN
+    with_k<64>(kk, [&](auto kc) {
+        constexpr int KV = decltype(kc)::value;
+        hipLaunchKernelGGL(k_knn<KV>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,
+                           ix->identity, q, qstride, nq, k, kk, mc, oidx, od2, fb.f);
+        hipLaunchKernelGGL(k_knn_coop<KV>, dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,
+                           ix->identity, q, qstride, k, kk, mc, oidx, od2, fb.f);
+    });
     PCP_LAUNCH_CHECK(ctx);
     // the far list's length for pcp_knn_last_far, stream-ordered before the list's block is reused
     PCP_HIP(ctx, hipMemcpyAsync(ctx->knn_far, fb.f.count, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
@@ -1695,77 +856,13 @@ int pcp_knn_last_far(pcp_ctx* ctx, int64_t* n) {
     return PCP_OK;
 }
 
-static uint32_t radius_cap(const pcp_index* ix, uint32_t max_nn) {
-    // max_nn == 0 or > total => unlimited (kd_tree.h:873-883)
-    if (max_nn == 0 || (int64_t)max_nn >= ix->n) return UINT32_MAX;
-    return max_nn;
-}
-
-int pcp_radius_count(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, int64_t nq, double radius,
-                     uint32_t max_nn, int32_t* ocnt) {
-    PCP_TRY(check_f64_index(ctx, ix));
-    if (nq < 0 || (nq > 0 && (!q || !ocnt)) || !(radius >= 0))
-        return set_error(ctx, PCP_ERR_ARG, "pcp_radius_count: bad arguments");
-    if (qstride == 0) qstride = 3 * sizeof(double);
-    if (nq == 0) return PCP_OK;
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    const double4* pts = (const double4*)ix->pts;
-    const uint32_t cap = radius_cap(ix, max_nn);
-    const double mc = cell_margin64(ix->g);
-    Tmp tmp(ctx);
-    if (radius_needs_far(ix, radius)) {
-        hipLaunchKernelGGL(k_radius_count<true>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
-                           nq, radius * radius, cap, mc, ocnt, FarList{nullptr, nullptr});
-    } else {
-        FarBuf fb;
-        PCP_TRY(fb.alloc(tmp, nq));
-        hipLaunchKernelGGL(k_radius_count<false>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q,
-                           qstride, nq, radius * radius, cap, mc, ocnt, fb.f);
-        hipLaunchKernelGGL(k_radius_count<true>, dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
-                           nq, radius * radius, cap, mc, ocnt, fb.f);
-    }
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
-}
-
-int pcp_radius_fill(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t qstride, int64_t nq, double radius,
-                    uint32_t max_nn, const int64_t* off, int32_t* oidx, double* od2) {
-    PCP_TRY(check_f64_index(ctx, ix));
-    if (nq < 0 || (nq > 0 && (!q || !off || !oidx || !od2)) || !(radius >= 0))
-        return set_error(ctx, PCP_ERR_ARG, "pcp_radius_fill: bad arguments");
-    (void)max_nn;  // row lengths were fixed by the count pass
-    if (qstride == 0) qstride = 3 * sizeof(double);
-    if (nq == 0) return PCP_OK;
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    const double4* pts = (const double4*)ix->pts;
-    const double mc = cell_margin64(ix->g);
-    const uint32_t cap = radius_cap(ix, max_nn);
-    Tmp tmp(ctx);
-    if (radius_needs_far(ix, radius)) {
-        hipLaunchKernelGGL(k_radius_fill<true>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
-                           nq, radius * radius, cap, mc, off, oidx, od2, FarList{nullptr, nullptr});
-    } else {
-        FarBuf fb;
-        PCP_TRY(fb.alloc(tmp, nq));
-        hipLaunchKernelGGL(k_radius_fill<false>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, ix->g, pts, q,
-                           qstride, nq, radius * radius, cap, mc, off, oidx, od2, fb.f);
-        hipLaunchKernelGGL(k_radius_fill<true>, dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, q, qstride,
-                           nq, radius * radius, cap, mc, off, oidx, od2, fb.f);
-    }
-    hipLaunchKernelGGL(k_sort_rows, dim3(grid_for((nq + 3) / 4, 1, 1 << 16)), dim3(256), 0, ctx->stream, off, nq, cap,
-                       oidx, od2, ix->mapping, ix->identity);
-    PCP_LAUNCH_CHECK(ctx);
-    return PCP_OK;
-}
-
 int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, int64_t n_out) {
     PCP_TRY(check_f64_index(ctx, ix));
     ctx->nrm_mode = 0;
     if (k <= 0 || n_out < 0 || (n_out > 0 && !out)) return set_error(ctx, PCP_ERR_ARG, "pcp_normals_knn: bad arguments");
     if (n_out < ix->n_in) return set_error(ctx, PCP_ERR_CAPACITY, "pcp_normals_knn: n_out < cloud size");
     const int kk = (int)(k < ix->n ? k : ix->n);
-    const int K = pick_k(kk);
-    if (!K || K > 32) return set_error(ctx, PCP_ERR_UNSUPPORTED, "pcp_normals_knn: k=%d > 32 not supported yet", k);
+    if (kk > 32) return set_error(ctx, PCP_ERR_UNSUPPORTED, "pcp_normals_knn: k=%d > 32 not supported yet", k);
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     if (n_out > 0) hipLaunchKernelGGL(k_plane_default, dim3(blocks_for(n_out)), dim3(kB), 0, ctx->stream, out, n_out);
     if (ix->n == 0 || kk <= 3) return PCP_OK;  // rpca's N > 3 guard (calculate_feature.cpp:237)
@@ -1776,12 +873,20 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
     FarBuf fb;
     PCP_TRY(fb.alloc(tmp, ix->n, true));
     const int tile_R = kk <= 8 ? 1 : 2;  // the tile's window half-width in cells
-    if (ix->g.dense) {
-        unsigned long long* st = nullptr;  // per-phase counters of profiling builds (PCP_NORMALS_STATS)
+    // per-phase counters of profiling builds (PCP_NORMALS_STATS): the tile's [0, 4) and [20, 22),
+    // the far pass's [4, 20)
+    unsigned long long* st = nullptr;
 #if PCP_NORMALS_STATS
-        PCP_TRY(tmp.get(&st, 24));
-        PCP_HIP(ctx, hipMemsetAsync(st, 0, 24 * sizeof(unsigned long long), ctx->stream));
+    PCP_TRY(tmp.get(&st, 24));
+    PCP_HIP(ctx, hipMemsetAsync(st, 0, 24 * sizeof(unsigned long long), ctx->stream));
 #endif
+    // the wave-per-query pass over the queries of `list`
+    auto far_pass = [&](auto kc, const FarList& list) {
+        constexpr int KV = decltype(kc)::value;
+        hipLaunchKernelGGL(k_normals_coop<KV>, dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,
+                           ix->identity, ix->pos_of_j, kk, mc, out, n_out, list, st ? st + 4 : nullptr);
+    };
+    if (ix->g.dense) {
         const unsigned nbt = (unsigned)std::min<int64_t>((ix->n + 63) / 64, 1 << 20);
         // brick order of the queries: (brick key, sorted position) radix-sorted
         uint32_t *k0, *k1, *v0, *order;
@@ -1804,21 +909,15 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
         // the tile's uncertified queries: the lane-per-query near pass (cell rings), its own
         // deferrals then the wave-per-query pass (all of them straight to the wave-per-query pass
         // measured slower)
-#define LAUNCH_TILE(KV)                                                                                          \
-        hipLaunchKernelGGL((k_normals_tile<KV>), dim3(nbt), dim3(64), 0, ctx->stream, ix->g, pts, ix->mapping,      \
-                           ix->identity, ix->n, kk, tile_R, mc, out, n_out, fb.f, st, order);                    \
-        hipLaunchKernelGGL((k_normals<KV, false, true>), dim3(blocks_for(ix->n)), dim3(kB), 0, ctx->stream, ix->g,  \
-                           pts, ix->mapping, ix->identity, ix->pos_of_j, ix->n, kk, mc, out, n_out, fb2.f, fb.f);   \
-        hipLaunchKernelGGL((k_normals_coop<KV>), dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts,            \
-                           ix->mapping, ix->identity, ix->pos_of_j, kk, mc, out, n_out, fb2.f,                     \
-                           st ? st + 4 : nullptr)
-        switch (K) {
-            case 1: case 4: LAUNCH_TILE(4); break;
-            case 8: LAUNCH_TILE(8); break;
-            case 16: LAUNCH_TILE(16); break;
-            default: LAUNCH_TILE(32); break;
-        }
-#undef LAUNCH_TILE
+        with_k<32>(kk, [&](auto kc) {
+            // the tile has no K = 1: 1 and 4 both use 4
+            constexpr int KV = decltype(kc)::value < 4 ? 4 : decltype(kc)::value;
+            hipLaunchKernelGGL(k_normals_tile<KV>, dim3(nbt), dim3(64), 0, ctx->stream, ix->g, pts, ix->mapping,
+                               ix->identity, ix->n, kk, tile_R, mc, out, n_out, fb.f, st, order);
+            hipLaunchKernelGGL((k_normals<KV, true>), dim3(blocks_for(ix->n)), dim3(kB), 0, ctx->stream, ix->g, pts,
+                               ix->mapping, ix->identity, ix->pos_of_j, ix->n, kk, mc, out, n_out, fb2.f, fb.f);
+            far_pass(std::integral_constant<int, KV>{}, fb2.f);
+        });
         hipLaunchKernelGGL(k_keep_deferred, dim3(1), dim3(1), 0, ctx->stream, fb.f.count, fb2.f.count,
                            ctx->nrm_deferred);
         PCP_LAUNCH_CHECK(ctx);
@@ -1842,19 +941,12 @@ int pcp_normals_knn(pcp_ctx* ctx, const pcp_index* ix, int k, pcp_plane* out, in
 #endif
         return PCP_OK;
     }
-#define LAUNCH_NRM(KV)                                                                                              \
-    hipLaunchKernelGGL((k_normals<KV, false>), dim3(blocks_for(ix->n)), dim3(kB), 0, ctx->stream, ix->g, pts,          \
-                       ix->mapping, ix->identity, ix->pos_of_j, ix->n, kk, mc, out, n_out, fb.f);                      \
-    hipLaunchKernelGGL((k_normals_coop<KV>), dim3(kFarBlocks), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,       \
-                       ix->identity, ix->pos_of_j, kk, mc, out, n_out, fb.f)
-    switch (K) {
-        case 1: LAUNCH_NRM(1); break;
-        case 4: LAUNCH_NRM(4); break;
-        case 8: LAUNCH_NRM(8); break;
-        case 16: LAUNCH_NRM(16); break;
-        default: LAUNCH_NRM(32); break;
-    }
-#undef LAUNCH_NRM
+    with_k<32>(kk, [&](auto kc) {
+        constexpr int KV = decltype(kc)::value;
+        hipLaunchKernelGGL(k_normals<KV>, dim3(blocks_for(ix->n)), dim3(kB), 0, ctx->stream, ix->g, pts, ix->mapping,
+                           ix->identity, ix->pos_of_j, ix->n, kk, mc, out, n_out, fb.f, FarList{nullptr, nullptr});
+        far_pass(kc, fb.f);
+    });
     hipLaunchKernelGGL(k_keep_deferred, dim3(1), dim3(1), 0, ctx->stream, fb.f.count, (const uint32_t*)nullptr,
                        ctx->nrm_deferred);
     PCP_LAUNCH_CHECK(ctx);
@@ -1877,19 +969,6 @@ int pcp_normals_knn_last_deferred(pcp_ctx* ctx, int64_t* tile_deferred, int64_t*
         *tile_deferred = -1;
         *far_queries = h[0];
     }
-    return PCP_OK;
-}
-
-int pcp_plane_fit_segments(pcp_ctx* ctx, const double* xyz, size_t stride, const int64_t* off, const int32_t* idx,
-                           int64_t nseg, pcp_plane* out) {
-    if (!ctx || nseg < 0 || (nseg > 0 && (!xyz || !off || !out)))
-        return set_error(ctx, PCP_ERR_ARG, "pcp_plane_fit_segments: bad arguments");
-    if (stride == 0) stride = 3 * sizeof(double);
-    if (nseg == 0) return PCP_OK;
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_plane_segments, dim3(blocks_for(nseg)), dim3(kB), 0, ctx->stream, xyz, stride, off, idx, nseg,
-                       out);
-    PCP_LAUNCH_CHECK(ctx);
     return PCP_OK;
 }
 
@@ -1927,54 +1006,6 @@ int pcp_nearest_query(pcp_ctx* ctx, const pcp_index* ix, const double* q, size_t
             if (hd[b] < bd || (hd[b] == bd && hi[b] < bi)) { bd = hd[b]; bi = hi[b]; }
         if (!rc && bd < init_bound) { *best_d2 = bd; *best_q = bi; }
     }
-    return rc;
-}
-
-int pcp_knn_lod(pcp_ctx* ctx, const void* cloud, int64_t n, const void* q, int64_t nq, int k, int32_t* oidx,
-                double* od2) {
-    if (!ctx || n < 0 || nq < 0 || k <= 0 || (n > 0 && !cloud) || (nq > 0 && (!q || !oidx || !od2)))
-        return set_error(ctx, PCP_ERR_ARG, "pcp_knn_lod: bad arguments");
-    if (n == 0 || nq == 0) return PCP_OK;
-    const int kk = (int)(k < n ? k : n);
-    const int K = pick_k(kk);
-    if (!K || K > 32) return set_error(ctx, PCP_ERR_UNSUPPORTED, "pcp_knn_lod: k=%d > 32 not supported yet", k);
-    PCP_HIP(ctx, hipSetDevice(ctx->device));
-    // c = Vector3i truncation of the centroid (kd_tree_lod/kd_tree.cpp:33-37)
-    double c[4];
-    uint32_t cnt = 0;
-    PCP_TRY(centroid_aos48_dev(ctx, cloud, n, 1, c, &cnt));
-    const int ci0 = (int)c[0], ci1 = (int)c[1], ci2 = (int)c[2];
-    float* v = nullptr;
-    Tmp tmp(ctx);
-    PCP_TRY(tmp.get(&v, 3 * (size_t)n));
-    hipLaunchKernelGGL(k_lod_vertices, dim3(blocks_for(n)), dim3(kB), 0, ctx->stream, (const char*)cloud, n, ci0, ci1,
-                       ci2, v);
-    pcp_index* fi = nullptr;
-    pcp_index* di = nullptr;
-    int rc = pcp_index_build_f32(ctx, v, 3 * sizeof(float), n, 0.0, &fi);
-    if (rc == PCP_OK) rc = pcp_index_build_f64(ctx, (const double*)cloud, PCP_AOS48_STRIDE, n, nullptr, 0, 0.0, &di);
-    if (rc == PCP_OK) {
-        const GridDesc& gf = fi->g;
-        const int nmax = std::max(gf.n[0], std::max(gf.n[1], gf.n[2]));
-        const float mcf = 1e-5f + 8e-7f * (float)nmax;
-#define LAUNCH_LOD(KV)                                                                                     \
-    hipLaunchKernelGGL(k_lod<KV>, dim3(blocks_for(nq)), dim3(kB), 0, ctx->stream, fi->g, (const float4*)fi->pts, \
-                       di->g, (const double4*)di->pts, di->mapping, di->identity, (const char*)cloud, n,           \
-                       (const char*)q, nq, k, kk, mcf, cell_margin64(di->g), ci0, ci1, ci2, oidx, od2)
-        switch (K) {
-            case 1: LAUNCH_LOD(1); break;
-            case 4: LAUNCH_LOD(4); break;
-            case 8: LAUNCH_LOD(8); break;
-            case 16: LAUNCH_LOD(16); break;
-            default: LAUNCH_LOD(32); break;
-        }
-#undef LAUNCH_LOD
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = hip_fail(ctx, e, "k_lod", __FILE__, __LINE__);
-    }
-    if (fi) pcp_index_destroy(fi);
-    if (di) pcp_index_destroy(di);
     return rc;
 }
 

@@ -1,4 +1,5 @@
-// F1 PCA core shared by the normals kernels (knn.hip) and the robust RPCA normals (rpca.hip).
+// F1 PCA core shared by the normals kernels (knn.hip), the per-segment plane fit (plane_fit.hip)
+// and the robust RPCA normals (rpca.hip).
 #pragma once
 #include "common.hpp"
 
@@ -100,5 +101,24 @@ __device__ inline void plane_from_cov(const double C[9], double xa, double ya, d
     out.curvature = (float)(l3 / (l1 + l2 + l3));  // :199
 }
 
+// The plane of `count` points visited one after another: the mean summed in that order (:131-142),
+// then the six sums of the centred X X^T in the same order (:143-164), then plane_from_cov.  The
+// order of the additions is the contract.  each(use) calls use(x, y, z) once per point, in
+// sequence order, and is run twice (every point is fetched twice); it is a walk and not an
+// index -> point map because a register top-k (topk.hpp) can only be walked.
+template <typename N, typename Each>
+__device__ __forceinline__ void plane_from_sequence(N count, Each&& each, pcp_plane& out) {
+    double xa = 0, ya = 0, za = 0;
+    each([&](double x, double y, double z) { xa += x; ya += y; za += z; });
+    xa /= count; ya /= count; za /= count;
+    double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
+    each([&](double x, double y, double z) {
+        const double x0 = x - xa, x1 = y - ya, x2 = z - za;
+        c00 += x0 * x0; c01 += x0 * x1; c02 += x0 * x2;
+        c11 += x1 * x1; c12 += x1 * x2; c22 += x2 * x2;
+    });
+    const double C[9] = {c00, c01, c02, c01, c11, c12, c02, c12, c22};
+    plane_from_cov(C, xa, ya, za, out);
+}
 
 }  // namespace pcp

@@ -139,6 +139,27 @@ def test_knn_aos48_and_small(ctx):
     assert (gi.cpu().numpy()[:, 5:] == -1).all()
 
 
+def test_knn_bucket_edges(ctx):
+    """Every k at which pcp_knn changes its compile-time list size (1, 4, 8, 16, 32, 64), and the
+    k just above each: the list that serves k must hold at least k entries.  More than 64 points,
+    so k = 65 is not clamped and is PCP_ERR_UNSUPPORTED."""
+    import knn_ref
+    from pointcloudprocess_amd import _lib, ops
+    xyz = _cloud(300, 101)
+    q = _cloud(64, 102)
+    ix = ops.GridIndex(ctx, _dev(ctx, xyz))
+    ref = knn_ref.ref_knn(xyz, q, 64)
+    for k in (1, 2, 4, 5, 8, 9, 16, 17, 32, 33, 64):
+        gi, gd = ops.knn(ix, _dev(ctx, q), k)
+        gi, gd = gi.cpu().numpy(), gd.cpu().numpy()
+        ei, ed = ref[0][:, :k], ref[1][:, :k]  # (d2, index) is a total order: a prefix of the longer row
+        assert np.array_equal(gi, ei), f"k={k}: {(gi != ei).any(1).sum()} rows differ"
+        assert np.array_equal(gd, ed), f"k={k}"
+    with pytest.raises(_lib.PcpError) as err:
+        ops.knn(ix, _dev(ctx, q), 65)
+    assert err.value.code == -5  # PCP_ERR_UNSUPPORTED
+
+
 def test_knn_sparse_grid(ctx):
     """Two clusters 5 km apart: the bounding grid is too large for a dense table."""
     from pointcloudprocess_amd import ops
@@ -223,6 +244,30 @@ def test_knn_lod(ctx, offset):
         ei, ed = ora.knn_lod(cloud, qc[i:i + 1], k)
         assert np.array_equal(gi[i], ei), f"query {i}"
         assert np.array_equal(gd[i], ed), f"query {i}"
+
+
+def test_knn_lod_bucket_edges(ctx):
+    """test_knn_lod's cloud at its smaller offset, at every k where pcp_knn_lod changes its
+    compile-time list size (1, 4, 8, 16, 32) and the k just above each; k = 33 has no list."""
+    from pointcloudprocess_amd import _lib, ops
+    rng = np.random.default_rng(51)
+    off = np.array((1234.3, -845.7, 12.1))
+    xyz = rng.uniform(0, 30, (20_000, 3)) + off
+    xyz = xyz.astype(np.float32).astype(np.float64)
+    cloud = ora.make_cloud(xyz)
+    qx = np.concatenate([xyz[:40] + 0.003, rng.uniform(0, 30, (40, 3)) + off])
+    qc = ora.make_cloud(qx)
+    dc, dq = ops.cloud_to_device(cloud, ctx.device), ops.cloud_to_device(qc, ctx.device)
+    for k in (1, 4, 5, 8, 9, 16, 17, 32):
+        gi, gd = ops.knn_lod(ctx, dc, dq, k)
+        gi, gd = gi.cpu().numpy(), gd.cpu().numpy()
+        for i in range(len(qc)):
+            ei, ed = ora.knn_lod(cloud, qc[i:i + 1], k)
+            assert np.array_equal(gi[i], ei), f"k={k} query {i}"
+            assert np.array_equal(gd[i], ed), f"k={k} query {i}"
+    with pytest.raises(_lib.PcpError) as err:
+        ops.knn_lod(ctx, dc, dq, 33)
+    assert err.value.code == -5  # PCP_ERR_UNSUPPORTED
 
 
 def test_nearest_query(ctx):

@@ -45,7 +45,7 @@ in one launch):
                     query 299,999 (the first wins), init_bound equal to the winning d2 (strict)
                     and an ulp above it, NaN rows, an all-NaN set.
 
-Checked once against builds of knn.hip with one change each (wrong rows only, nothing out of
+Checked once against builds of knn.hip (the far pass is now knn_coop.hpp) with one change each (wrong rows only, nothing out of
 bounds); the tests that failed, of 55:
 
   coop_merge comparing d2 alone              every k of tie_lattice_far on both tables, of

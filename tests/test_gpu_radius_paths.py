@@ -45,7 +45,7 @@ mapping, 4 row ordering in k_sort_rows, 5 max_nn, 6 strict d2 < r*r, 7 odd queri
   normals          ops.normals_radius over rows of 1, 2, 3, 4 and > 1024 points (asserted).
   scan             8.  pcp_scan_counts around one tile, two and three levels, totals past 2^32.
 
-Checked once against builds of knn.hip with one comparison changed each: `<=` for the strict
+Checked once against builds of radius.hip (then part of knn.hip) with one comparison changed each: `<=` for the strict
 `<` (fails lattice, lattice_mapped, one_finite, switch_lattice, the lattice normals), the bitonic
 sort comparing d2 alone (lattice, lattice_mapped, duplicates, switch_lattice, the normals), no
 mapping after the in-place sort (ladder_nan on both grids), the insertion rows' tie at the cut
