@@ -192,6 +192,23 @@ int pcp_knn_lod(pcp_ctx* ctx, const void* cloud_aos48_dev, int64_t n, const void
 /* PointCloudHelper::getMinMax3D(cloud, Vector4d&, Vector4d&) (point_cloud_helper.h:59-90). */
 int pcp_minmax_aos48(pcp_ctx* ctx, const void* in_dev, int64_t n, int is_dense,
                      double min_host[4], double max_host[4]);
+/* getMinMax3D of transformPointCloud(segment s, T_s) for every segment of a span of AoS48 records,
+ * without the moved copies: row s of min_host / max_host (nseg x 4) is what pcp_minmax_aos48 returns
+ * for pcp_transform_aos48(records [off[s], off[s + 1]), T_host + 16 s), both with is_dense -- the
+ * same arithmetic ((r0 x + r1 y) + r2 z) + t in fp64, a non-finite point left alone by the transform
+ * and skipped by the min/max when !is_dense, data[3] untransformed, DBL_MAX / DBL_MIN for a segment
+ * without a counted point (the reference's DBL_MIN start of the max included).  Min and max are exact
+ * in any order, so the rows agree bit for bit (up to the sign of a zero, which no order fixes).
+ * T_host == NULL is the identity for every segment, run through the same arithmetic.  Segment rules
+ * are pcp_icp_batch_create's (I5): offsets start at 0, end at n, never decrease; 0 <= nseg <= 65535;
+ * empty segments are legal; PCP_ERR_ARG otherwise, and a rejected call writes nothing.  nseg == 0
+ * writes nothing.  One pass over the records in two launches whatever nseg is (tiles of 2048
+ * records that never straddle a segment; then one workgroup per segment over its tiles' rows), one
+ * nseg x 64 byte copy back and one host synchronisation. */
+int pcp_minmax_segments_aos48(pcp_ctx* ctx, const void* in_aos48_dev, int64_t n,
+                              const int64_t* seg_offsets_host /* nseg + 1 */, int nseg, int is_dense,
+                              const double* T_host /* nseg x 16 row-major, NULL = identity */,
+                              double* min_host /* nseg x 4 */, double* max_host /* nseg x 4 */);
 /* compute3DCentroid (point_cloud_helper.h:193-230): the reference's sequential left fold,
  * bit for bit, evaluated as a parallel scan of exact chunk transfer maps (fold.hip). */
 int pcp_centroid_aos48(pcp_ctx* ctx, const void* in_dev, int64_t n, int is_dense,
@@ -859,8 +876,8 @@ int pcp_icp_batch_run_plane_rtrimmed_dev(pcp_ctx* ctx, pcp_icp_batch* batch, con
  *   the per-call guard, so pcp_ctx_alloc_stats balances on every path.
  *
  * Not here: a fused search + accumulate kernel; per-segment do_scale or trim parameters; the
- * plane-residual trim (it needs a plane table); pcp_get_rot_icp-style wrappers with fp64 centring
- * (the caller centres, as for every fp32 ICP entry). */
+ * plane-residual trim (it needs a plane table).  The pcp_get_rot_icp-style wrapper with fp64
+ * centring is I5d. */
 #define PCP_ICP_ACC 24
 int pcp_icp_batch_accumulate(pcp_ctx* ctx, pcp_icp_batch* batch, const double* T_dev /* nseg x 16 */,
                              const uint64_t* keys_dev /* nq, ORIGINAL order */,
@@ -875,6 +892,63 @@ int pcp_icp_batch_run_trimmed_dev(pcp_ctx* ctx, pcp_icp_batch* batch, const floa
                                   size_t t_stride_bytes, int64_t n_target, double* T_dev, float rmax,
                                   float frac, float mult, float d_floor, int iters, int do_scale,
                                   double* stats_dev, uint64_t* trim_dev /* nseg x 4: last iteration */);
+
+/* ----------------------------------------------------------------------- I5d: get_rot_icp over a span of frames
+ * pcp_get_rot_icp's staging around the loops of I5c, for the caller those loops were built for:
+ * do_mul_frame_icp with is_do_sep_icp (main_blend.cpp:839-904) re-registers every frame of a span,
+ * each moved by its own fp64 pose, against the map around it.  One call registers nseg AoS48 frames
+ * (records [off[s], off[s + 1]) of frames_aos48_dev, at map coordinates) against ONE AoS48 target
+ * and returns nseg un-centred 4x4s and nseg errors.  The contract is the build's own, as I1's.
+ *
+ * Centre.  c = pcp_centroid_aos48(target, target_is_dense): the sequential-fold centroid of the
+ *   TARGET ALONE.  CONTRACT DIFFERENCE from pcp_get_rot_icp, whose c is the joint centroid of
+ *   src ++ temp: the frames lie inside the target's box by construction (the caller cuts the target
+ *   around them), so the target's centroid centres both to fp32's precision, and it needs no pass
+ *   over the moved frames.  Any c is removed again by the un-centring below; it only decides where
+ *   the fp32 roundings fall.
+ * Staging.  For record i of segment s, in one launch whatever nseg is:
+ *     moved_i = ((r0 x + r1 y) + r2 z) + t in fp64 with T0_host + 16 s (pcp_transform_aos48's
+ *       arithmetic; T0_host == NULL: the identity, through the same arithmetic); the point is left as
+ *       it is when !frames_is_dense and it is non-finite;
+ *     q32_i = ((float)(moved.x - c0), (float)(moved.y - c1), (float)(moved.z - c2)), packed xyz.
+ *   A non-finite q32_i is an ordinary query that gets no key (I5).  The target is centred the same
+ *   way without a pose: (float)(p - c).
+ * Loop.  pcp_index_build_f32(cell_size) over the centred target, pcp_icp_batch_create over the
+ *   staged queries with seg_offsets_host, identity poses and zeroed stats, then pcp_icp_batch_run_dev
+ *   (rmax, iters, do_scale), or pcp_icp_batch_run_trimmed_dev when trim_host = {frac, mult, d_floor}
+ *   is given; the centred fp32 target is the caller-order cloud of I5c.  Those entries are called as
+ *   they are, so poses and stats are bit for bit what a caller gets who stages the same fp32 arrays
+ *   and calls them.
+ * Results.  With T_s, stats_s the pose and stats row of segment s after the loop:
+ *     mat_rot[s] = T_s with t'_r = (t_r - rcv) + c_r, rcv = R_r0 c0; rcv += R_r1 c1; rcv += R_r2 c2
+ *       (pcp_get_rot_icp's order), when stats_s[3] > 0; the exact identity for a segment that never
+ *       solved (iters == 0, fewer than 3 pairs);
+ *     err[s] = (float)stats_s[1] when stats_s[0] == 0 and stats_s[3] > 0, else -1;
+ *     steps[s] = stats_s[3] (optional); kept[s] = the kept count of the last iteration's trim row
+ *       (optional; 0 without trim_host or with iters == 0).
+ *   The caller composes final_s = mat_rot[s] * T0_s.  One device-to-host copy brings poses, stats
+ *   and trim rows.
+ * Correspondences.  Per-frame registration (pcp_get_rot_icp against the map points of each frame's
+ *   own +-3 m box) and this call pair a query image with the same map point as long as that image
+ *   stays at least rmax inside its frame's own box: every point within rmax of it is then in both
+ *   targets.  The two results then differ only by the fp32 centring (another c) and the order of
+ *   the sums.  A frame whose surroundings hold no map point gets err = -1 and the identity here; the
+ *   reference skips such a frame because its cache_t is empty.
+ * Edges.  rmax <= 0: PCP_ERR_UNSUPPORTED (as pcp_get_rot_icp; nothing is written).  nseg == 0:
+ *   PCP_OK, nothing written.  n_target == 0 or nq == 0: PCP_OK, identities, err = -1, steps = 0,
+ *   kept = 0.  PCP_ERR_ARG for: a null context or seg_offsets_host; a null cloud with a positive
+ *   size; negative sizes; offsets that break pcp_icp_batch_create's rules (nq in place of its nq);
+ *   nseg outside [0, 65535]; iters < 0; trim_host values that break I5b's rules; a null mat_rot_host
+ *   or err_host with nseg > 0.  Sizes beyond pcp_icp_check_sizes's limits return its code.  Every
+ *   check comes before the first device call and a rejected call writes nothing.  The index, the
+ *   batch handle and every temporary are released on every path: pcp_ctx_alloc_stats balances. */
+int pcp_get_rot_icp_batch(pcp_ctx* ctx, const void* target_aos48_dev, int64_t n_target, int target_is_dense,
+                          const void* frames_aos48_dev, int64_t nq, int frames_is_dense,
+                          const int64_t* seg_offsets_host /* nseg + 1 */, int nseg,
+                          const double* T0_host /* nseg x 16, NULL = identity */,
+                          float rmax, int iters, int do_scale, const float* trim_host /* NULL or {frac, mult, d_floor} */,
+                          double cell_size, double* mat_rot_host /* nseg x 16 */, float* err_host /* nseg */,
+                          int32_t* steps_host /* nseg, optional */, int64_t* kept_host /* nseg, optional, trim only */);
 
 /* ----------------------------------------------------------------------- I4: pose lines
  * Host-only (no device work): n frames' poses as row-major 4x4 doubles, rots[16 * i].

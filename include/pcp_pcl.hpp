@@ -775,6 +775,52 @@ public:
             for (int col = 0; col < 4; col++) mat_rot(r, col) = Mh[4 * r + col];
         return err;
     }
+    // get_rot_icp for every frame of a span in one call (pcp.h I5d; not in the reference): frame s,
+    // moved by T0s[s], is registered against `cache` (point-to-point, no scale), all frames in the
+    // same three launches per iteration.  out_rots[s] receives the un-centred 4x4 (the frame's
+    // pose is out_rots[s] * T0s[s]) and out_errs[s] the RMS pair distance, -1 for a frame that
+    // found no pairs (its out_rots[s] is the identity).  The centre is the cache's own centroid, not
+    // get_rot_icp's joint one.  A null frame counts as empty.  Returns false, with identities and
+    // -1s, when the call is rejected (maxdist <= 0, T0s.size() != frames.size()).
+    template <class M>
+    static bool get_rot_icp_batch(CloudPtr cache, const std::vector<CloudPtr>& frames, const std::vector<M>& T0s,
+                                  std::vector<M>& out_rots, std::vector<float>& out_errs, int iters = kIcpIters,
+                                  float maxdist = kIcpMaxDist) {
+        const size_t B = frames.size();
+        out_rots.resize(B);
+        out_errs.assign(B, -1.0f);
+        for (size_t s = 0; s < B; s++)
+            for (int r = 0; r < 4; r++)
+                for (int col = 0; col < 4; col++) out_rots[s](r, col) = (r == col) ? 1.0 : 0.0;
+        if (!cache || T0s.size() != B || B > 65535 || !(maxdist > 0.f) || iters < 0) return false;
+        if (B == 0) return true;
+        std::vector<int64_t> off(B + 1, 0);
+        std::vector<CloudItem> span;
+        std::vector<double> T0(16 * B), Mh(16 * B);
+        bool dense = true;
+        for (size_t s = 0; s < B; s++) {
+            if (frames[s]) {
+                span.insert(span.end(), frames[s]->points.begin(), frames[s]->points.end());
+                dense = dense && frames[s]->is_dense;
+            }
+            off[s + 1] = (int64_t)span.size();
+            for (int r = 0; r < 4; r++)
+                for (int col = 0; col < 4; col++) T0[16 * s + 4 * r + col] = T0s[s](r, col);
+        }
+        pcp_ctx* c = detail::Device::get().ctx();
+        std::lock_guard<std::mutex> lk(detail::Device::get().mutex());
+        detail::DevBuf t, f;
+        t.upload(cache->points.data(), cache->points.size() * sizeof(CloudItem));
+        f.upload(span.data(), span.size() * sizeof(CloudItem));
+        const int rc = pcp_get_rot_icp_batch(c, t.ptr(), (int64_t)cache->size(), cache->is_dense ? 1 : 0, f.ptr(),
+                                             (int64_t)span.size(), dense ? 1 : 0, off.data(), (int)B, T0.data(), maxdist,
+                                             iters, 0, nullptr, 0.0, Mh.data(), out_errs.data(), nullptr, nullptr);
+        if (rc != PCP_OK) return false;
+        for (size_t s = 0; s < B; s++)
+            for (int r = 0; r < 4; r++)
+                for (int col = 0; col < 4; col++) out_rots[s](r, col) = Mh[16 * s + 4 * r + col];
+        return true;
+    }
     // point_dis2 (point_cloud_helper.h:20): pow(dx,2)+pow(dy,2)+pow(dz,2)
     static double point_dis2(const PointXYZRGBA& p1, const PointXYZRGBA& p2) {
         const double dx = p1.x - p2.x, dy = p1.y - p2.y, dz = p1.z - p2.z;

@@ -150,6 +150,9 @@ SIGNATURES = [
     ("pcp_icp_batch_run_dev", _i32, [_vp, _vp, _vp, _sz, _i64, _vp, _f32, _i32, _i32, _vp]),
     ("pcp_icp_batch_run_trimmed_dev", _i32, [_vp, _vp, _vp, _sz, _i64, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp,
                                              _vp]),
+    ("pcp_minmax_segments_aos48", _i32, [_vp, _vp, _i64, _P(_i64), _i32, _i32, _P(_f64), _P(_f64), _P(_f64)]),
+    ("pcp_get_rot_icp_batch", _i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _P(_i64), _i32, _P(_f64), _f32, _i32, _i32,
+                                     _P(_f32), _f64, _P(_f64), _P(_f32), _P(_i32), _P(_i64)]),
 ]
 
 _lib = None

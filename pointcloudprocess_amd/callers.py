@@ -152,8 +152,28 @@ def _box_pad(ctx, cloud, pad):
     return (mn[0] - pad, mn[1] - pad, mn[2] - pad), (mx[0] + pad, mx[1] + pad, mx[2] + pad)
 
 
+def _sep_icp_batch(ctx, grid, clouds, rot, dense):
+    """The per-frame step of do_mul_frame_icp (main_blend.cpp:839-904) for all frames at once: the
+    boxes of the frames moved by rot, the map cache around their union +- 3 m, one batched
+    get_rot_icp(cache, moved_s, do_scale = false); returns rot_split_s @ rot per frame."""
+    import torch
+    if not clouds:
+        return []
+    off = np.concatenate([[0], np.cumsum([c.shape[0] for c in clouds])]).astype(np.int64)
+    span = torch.cat(clouds).contiguous()
+    mn, mx = ops.minmax_segments(ctx, span, off, T=rot, is_dense=dense)
+    seen = (mn[:, :3] <= mx[:, :3]).all(axis=1)  # a frame without a counted point keeps DBL_MAX / DBL_MIN
+    if not seen.any():
+        return [rot for _ in clouds]
+    lo, hi = mn[seen, :3].min(axis=0) - 3.0, mx[seen, :3].max(axis=0) + 3.0
+    cache = grid.get_cloud_with_pos(tuple(lo), tuple(hi))
+    _, mats, _, _ = ops.get_rot_icp_batch(ctx, cache.contiguous(), span, off, 0.25, T0=rot, iters=20, do_scale=False,
+                                          frames_dense=dense)
+    return [m @ rot for m in mats]
+
+
 def do_mul_frame_icp(ctx, line, stamp_file, start_index, end_index, grid, valid_count, min_icp_threshold,
-                     is_do_sep_icp=False, is_mul_seg=False, is_shaft_filter=False, load_cloud=None):
+                     is_do_sep_icp=False, is_mul_seg=False, is_shaft_filter=False, load_cloud=None, sep_batch=False):
     """do_mul_frame_icp (main_blend.cpp:641-931) on the device path.  line: the pose line, a list
     of dicts {stamp, matrix (4x4), icperr} (g_status._clouds_stamp_rot_line; matrices are
     updated in place, at the first entry of each stamp as get_cloud_rot_with_stamp does);
@@ -162,7 +182,14 @@ def do_mul_frame_icp(ctx, line, stamp_file, start_index, end_index, grid, valid_
     is_dense as the reference's reader does); a plain tensor counts as dense when its xyz are
     all finite.  The joint frame's is_dense is the AND of the
     loaded clouds' (PointCloud::operator+=, point_cloud.h:130-147).  Returns (dis, rot) of
-    the joint registration."""
+    the joint registration.
+
+    sep_batch (only with is_do_sep_icp): the per-frame registrations in one call each of
+    ops.minmax_segments and ops.get_rot_icp_batch (pcp.h I5d) instead of one transform, box, map
+    cut, index and ICP handle per frame: the map is cut once, around the union of the frames'
+    +-3 m boxes, and every frame is registered against it.  A frame's pairs are those of the
+    per-frame path as long as its points stay 0.25 m inside its own box; the poses then differ
+    by the fp32 centring and the order of the sums."""
     import torch
     from . import pcd as _pcd
     from . import segments as _seg
@@ -198,6 +225,12 @@ def do_mul_frame_icp(ctx, line, stamp_file, start_index, end_index, grid, valid_
     by_stamp = {}
     for i, e in enumerate(line):
         by_stamp.setdefault(e["stamp"], i)
+    if is_do_sep_icp and sep_batch:
+        finals = _sep_icp_batch(ctx, grid, clouds, rot, dense)
+        for (st, _), final in zip(frames, finals):
+            if st in by_stamp:
+                line[by_stamp[st]]["matrix"] = np.array(final)
+        return dis, rot
     for (st, _), cloud in zip(frames, clouds):  # (:839-904)
         final = rot
         if is_do_sep_icp:

@@ -5,6 +5,8 @@
 //   VoxelGrid::applyFilter voxel_grid.h:811-1056     (V3)
 //   remove_duplicate  point_cloud_helper.cpp:42-63   (V4)
 //   get_rot_icp       point_cloud_helper.cpp:75-166  (I1, front-end of the ICP kernels)
+// and, for a span of segments with one pose each (not in the reference): the moved segments'
+// min/max (V, pcp_minmax_segments_aos48) and get_rot_icp's staging around the batch loops (I5d).
 //
 // All passes stream the 48-byte records once (HBM-bound).  The voxel sort is rocPRIM's
 // device radix sort (LSD, stable) on u32 voxel keys; keying, run detection and the
@@ -210,6 +212,167 @@ __global__ __launch_bounds__(kB) void k_centre_f32(const P48* in, int64_t n, dou
     }
 }
 
+// ---- passes over a span of segments, each with its own pose: one launch whatever nseg is.
+// The host cuts every segment into tiles of kSegTile records (segtab[nseg + 1 + s] = the first tile
+// of segment s, empty segments own none); a workgroup takes whole tiles, finds a tile's segment by
+// bisection of that table (uniform over the workgroup) and reads the segment's pose once per tile.
+constexpr int kSegTile = 2048;
+constexpr int kSegBlocks = 1 << 16;
+
+struct SegTile {
+    int s;
+    int64_t begin, end;  // records [begin, end) of the span
+};
+__device__ __forceinline__ SegTile seg_tile(const int64_t* segtab, int nseg, int64_t t) {
+    const int64_t* first = segtab + nseg + 1;
+    int lo = 0, hi = nseg;  // first[lo] <= t < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= t) lo = mid; else hi = mid;
+    }
+    SegTile r;
+    r.s = lo;
+    r.begin = segtab[lo] + (t - first[lo]) * kSegTile;
+    r.end = r.begin + kSegTile < segtab[lo + 1] ? r.begin + kSegTile : segtab[lo + 1];
+    return r;
+}
+__device__ __forceinline__ Xf load_xf(const double* T16) {
+    Xf x;
+#pragma unroll
+    for (int i = 0; i < 12; i++) x.m[i] = T16[i];
+    return x;
+}
+
+// the workgroup's min / max of 4 + 4 running values into dst[0..7] (k_minmax48's reduction)
+__device__ __forceinline__ void block_minmax8(const double mn[4], const double mx[4], double (*sm)[8], double* dst) {
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const double a0 = wave_min(mn[a]), a1 = wave_max(mx[a]);
+        if (ln == 0) { sm[wv][a] = a0; sm[wv][4 + a] = a1; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        double r = sm[0][threadIdx.x];
+        for (int w = 1; w < kB / 64; w++) r = threadIdx.x < 4 ? fmin(r, sm[w][threadIdx.x]) : fmax(r, sm[w][threadIdx.x]);
+        dst[threadIdx.x] = r;
+    }
+    __syncthreads();  // sm is reused by the caller's next tile
+}
+
+// V2 of transformPointCloud(segment s, T_s), per tile, without the moved copy: k_transform48's
+// rule (a non-finite point of a non-dense cloud stays as it is), then k_minmax48's (a non-finite
+// point of a non-dense cloud is skipped; data[3] rides along untransformed).
+__global__ __launch_bounds__(kB) void k_minmax_seg_tiles(const P48* in, const int64_t* segtab, int nseg,
+                                                         int64_t ntiles, const double* Ts, int is_dense,
+                                                         double* part /* ntiles x 8 */) {
+    __shared__ double sm[kB / 64][8];
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const SegTile st = seg_tile(segtab, nseg, t);
+        const Xf T = load_xf(Ts + 16 * (int64_t)st.s);
+        double mn[4] = {DBL_MAX, DBL_MAX, DBL_MAX, DBL_MAX}, mx[4] = {DBL_MIN, DBL_MIN, DBL_MIN, DBL_MIN};
+        for (int64_t i = st.begin + threadIdx.x; i < st.end; i += kB) {
+            const P48 p = in[i];
+            double v[4] = {p.x, p.y, p.z, p.w};
+            if (is_dense || finite3(p.x, p.y, p.z)) xform(T, p.x, p.y, p.z, v);
+            if (!is_dense && !finite3(v[0], v[1], v[2])) continue;
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+                if (v[a] < mn[a]) mn[a] = v[a];
+                if (mx[a] < v[a]) mx[a] = v[a];
+            }
+        }
+        block_minmax8(mn, mx, sm, part + 8 * t);
+    }
+}
+
+// one workgroup per segment: its tiles' rows into row s (an empty segment: DBL_MAX / DBL_MIN)
+__global__ __launch_bounds__(kB) void k_minmax_seg_rows(const double* part, const int64_t* segtab, int nseg,
+                                                        double* rows /* nseg x 8 */) {
+    __shared__ double sm[kB / 64][8];
+    const int s = blockIdx.x;
+    const int64_t* first = segtab + nseg + 1;
+    double mn[4] = {DBL_MAX, DBL_MAX, DBL_MAX, DBL_MAX}, mx[4] = {DBL_MIN, DBL_MIN, DBL_MIN, DBL_MIN};
+    for (int64_t t = first[s] + threadIdx.x; t < first[s + 1]; t += kB) {
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            const double lo = part[8 * t + a], hi = part[8 * t + 4 + a];
+            if (lo < mn[a]) mn[a] = lo;
+            if (mx[a] < hi) mx[a] = hi;
+        }
+    }
+    block_minmax8(mn, mx, sm, rows + 8 * (int64_t)s);
+}
+
+// I5d staging: q32_i = float(xform(T0_s, p_i) - c), k_transform48's rule for a non-finite point of
+// a non-dense cloud (it stays, and its fp32 image is non-finite: a query without a key), then
+// k_centre_f32's arithmetic.
+__global__ __launch_bounds__(kB) void k_stage_seg_f32(const P48* in, const int64_t* segtab, int nseg, int64_t ntiles,
+                                                      const double* Ts, int is_dense, double c0, double c1, double c2,
+                                                      float* v) {
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const SegTile st = seg_tile(segtab, nseg, t);
+        const Xf T = load_xf(Ts + 16 * (int64_t)st.s);
+        for (int64_t i = st.begin + threadIdx.x; i < st.end; i += kB) {
+            const P48 p = in[i];
+            double o[3] = {p.x, p.y, p.z};
+            if (is_dense || finite3(p.x, p.y, p.z)) xform(T, p.x, p.y, p.z, o);
+            v[3 * i + 0] = (float)(o[0] - c0);
+            v[3 * i + 1] = (float)(o[1] - c1);
+            v[3 * i + 2] = (float)(o[2] - c2);
+        }
+    }
+}
+
+}  // namespace
+
+namespace {
+
+// segment rules of pcp_icp_batch_create over a span of n records
+bool seg_offsets_ok(const int64_t* off, int nseg, int64_t n) {
+    if (!off || nseg < 0 || nseg > 65535 || off[0] != 0 || off[nseg] != n) return false;
+    for (int s = 0; s < nseg; s++)
+        if (off[s + 1] < off[s]) return false;
+    return true;
+}
+
+// The device tables of the segment passes: segtab = offsets (nseg + 1) ++ first tile per segment
+// (nseg + 1), Ts = nseg x 16 poses (the identity for a null T_host: the passes then run xform with
+// it, so a null pose and an explicit identity give the same bits).  The uploads read this object's
+// host arrays, so it waits for the stream before they go.
+struct SegTable {
+    pcp_ctx* ctx;
+    std::vector<int64_t> h;
+    std::vector<double> hT;
+    int64_t* segtab = nullptr;
+    double* Ts = nullptr;
+    int64_t ntiles = 0;
+    bool inflight = false;
+    explicit SegTable(pcp_ctx* c) : ctx(c) {}
+    ~SegTable() {
+        if (inflight) (void)hipStreamSynchronize(ctx->stream);
+    }
+    int upload(Tmp& tmp, const int64_t* off, int nseg, const double* T_host) {
+        h.assign(2 * ((size_t)nseg + 1), 0);
+        for (int s = 0; s <= nseg; s++) h[s] = off[s];
+        for (int s = 0; s < nseg; s++) {
+            h[(size_t)nseg + 1 + s] = ntiles;
+            ntiles += (off[s + 1] - off[s] + kSegTile - 1) / kSegTile;
+        }
+        h[2 * (size_t)nseg + 1] = ntiles;
+        hT.resize(16 * (size_t)nseg);
+        for (size_t i = 0; i < hT.size(); i++) hT[i] = T_host ? T_host[i] : (i % 16 % 5 == 0 ? 1.0 : 0.0);
+        PCP_TRY(tmp.get(&segtab, h.size()));
+        PCP_TRY(tmp.get(&Ts, hT.size()));
+        inflight = true;
+        PCP_HIP(ctx, hipMemcpyAsync(segtab, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        if (nseg > 0)
+            PCP_HIP(ctx, hipMemcpyAsync(Ts, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        return PCP_OK;
+    }
+    unsigned grid() const { return (unsigned)(ntiles < kSegBlocks ? (ntiles > 0 ? ntiles : 1) : kSegBlocks); }
+};
+
 }  // namespace
 
 int minmax_aos48_dev(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, double mn[4], double mx[4]) {
@@ -319,6 +482,36 @@ int pcp_minmax_aos48(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, doub
     if (!ctx || n < 0 || (n > 0 && !in) || !mn || !mx) return set_error(ctx, PCP_ERR_ARG, "pcp_minmax_aos48: bad arguments");
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     return minmax_aos48_dev(ctx, in, n, is_dense, mn, mx);
+}
+
+int pcp_minmax_segments_aos48(pcp_ctx* ctx, const void* in, int64_t n, const int64_t* seg_offsets, int nseg,
+                              int is_dense, const double* T_host, double* mn, double* mx) {
+    if (!ctx || n < 0 || (n > 0 && !in) || !seg_offsets_ok(seg_offsets, nseg, n) || (nseg > 0 && (!mn || !mx)))
+        return set_error(ctx, PCP_ERR_ARG, "pcp_minmax_segments_aos48: bad arguments");
+    if (nseg == 0) return PCP_OK;
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    Tmp tmp(ctx);
+    SegTable tab(ctx);
+    PCP_TRY(tab.upload(tmp, seg_offsets, nseg, T_host));
+    double *part = nullptr, *rows = nullptr;
+    PCP_TRY(tmp.get(&part, 8 * (size_t)tab.ntiles));
+    PCP_TRY(tmp.get(&rows, 8 * (size_t)nseg));
+    if (tab.ntiles > 0)
+        hipLaunchKernelGGL(k_minmax_seg_tiles, dim3(tab.grid()), dim3(kB), 0, ctx->stream, (const P48*)in,
+                           (const int64_t*)tab.segtab, nseg, tab.ntiles, (const double*)tab.Ts, is_dense, part);
+    hipLaunchKernelGGL(k_minmax_seg_rows, dim3(nseg), dim3(kB), 0, ctx->stream, (const double*)part,
+                       (const int64_t*)tab.segtab, nseg, rows);
+    PCP_LAUNCH_CHECK(ctx);
+    std::vector<double> h(8 * (size_t)nseg);
+    PCP_HIP(ctx, hipMemcpyAsync(h.data(), rows, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    tab.inflight = false;
+    for (int s = 0; s < nseg; s++)
+        for (int a = 0; a < 4; a++) {
+            mn[4 * s + a] = h[8 * (size_t)s + a];
+            mx[4 * s + a] = h[8 * (size_t)s + 4 + a];
+        }
+    return PCP_OK;
 }
 
 int pcp_centroid_aos48(pcp_ctx* ctx, const void* in, int64_t n, int is_dense, double c[4], uint32_t* count) {
@@ -451,6 +644,111 @@ int pcp_get_rot_icp(pcp_ctx* ctx, const void* src, int64_t ns, int src_dense, co
     if (icp) pcp_icp_destroy(icp);
     if (ix) pcp_index_destroy(ix);
     return rc;
+}
+
+// I5d: pcp_get_rot_icp's staging for a span of frames, each moved by its own fp64 pose, around the
+// point-to-point batch loops of I5c (called as they are).  The centre is the target's own centroid.
+int pcp_get_rot_icp_batch(pcp_ctx* ctx, const void* target, int64_t nt, int target_dense, const void* frames, int64_t nq,
+                          int frames_dense, const int64_t* seg_offsets, int nseg, const double* T0_host, float rmax,
+                          int iters, int do_scale, const float* trim, double cell_size, double* mat_rot, float* err,
+                          int32_t* steps, int64_t* kept) {
+    if (!ctx || nt < 0 || nq < 0 || (nt > 0 && !target) || (nq > 0 && !frames) || !seg_offsets_ok(seg_offsets, nseg, nq) ||
+        iters < 0 || (trim && !trim_args_ok(trim[0], trim[1], trim[2])) || (nseg > 0 && (!mat_rot || !err)))
+        return set_error(ctx, PCP_ERR_ARG, "pcp_get_rot_icp_batch: bad arguments");
+    if (int rc = pcp_icp_check_sizes(nt, nq))
+        return set_error(ctx, rc, "pcp_get_rot_icp_batch: target or frames too large (pcp_icp_check_sizes)");
+    if (!(rmax > 0.f))
+        return set_error(ctx, PCP_ERR_UNSUPPORTED,
+                         "pcp_get_rot_icp_batch: rmax must be > 0 (trimesh2's automatic maxdist = 0 is not provided)");
+    if (nseg == 0) return PCP_OK;
+    const size_t B = (size_t)nseg;
+    // poses (16 B), stats (4 B), trim rows (4 B u64, zero until a trimmed iteration writes them)
+    std::vector<double> pose(24 * B, 0.0);
+    for (size_t s = 0; s < B; s++)
+        for (int i = 0; i < 16; i += 5) pose[16 * s + i] = 1.0;
+    double* stats = pose.data() + 16 * B;
+    struct StreamWait {  // pose is read and written by stream-ordered copies: no return path frees it under one
+        pcp_ctx* ctx;
+        bool on = false;
+        ~StreamWait() {
+            if (on) (void)hipStreamSynchronize(ctx->stream);
+        }
+    } wait{ctx};
+    double c[4] = {0, 0, 0, 0};
+    if (nt > 0 && nq > 0) {
+        PCP_HIP(ctx, hipSetDevice(ctx->device));
+        PCP_TRY(centroid_aos48_dev(ctx, target, nt, target_dense, c, nullptr));
+        Tmp bufs(ctx);
+        // handles are destroyed on every path, the batch before its target index
+        struct Handles {
+            pcp_index* ix = nullptr;
+            pcp_icp_batch* batch = nullptr;
+            ~Handles() {
+                if (batch) pcp_icp_batch_destroy(batch);
+                if (ix) pcp_index_destroy(ix);
+            }
+        } h;
+        float *ft = nullptr, *fq = nullptr;
+        double* dpose = nullptr;
+        PCP_TRY(bufs.get(&ft, 3 * (size_t)nt));
+        PCP_TRY(bufs.get(&fq, 3 * (size_t)nq));
+        PCP_TRY(bufs.get(&dpose, pose.size()));
+        {
+            SegTable tab(ctx);
+            PCP_TRY(tab.upload(bufs, seg_offsets, nseg, T0_host));
+            hipLaunchKernelGGL(k_centre_f32, dim3(grid_for(nt, kB)), dim3(kB), 0, ctx->stream, (const P48*)target, nt,
+                               c[0], c[1], c[2], ft);
+            hipLaunchKernelGGL(k_stage_seg_f32, dim3(tab.grid()), dim3(kB), 0, ctx->stream, (const P48*)frames,
+                               (const int64_t*)tab.segtab, nseg, tab.ntiles, (const double*)tab.Ts, frames_dense, c[0],
+                               c[1], c[2], fq);
+            PCP_LAUNCH_CHECK(ctx);
+            PCP_TRY(pcp_index_build_f32(ctx, ft, 3 * sizeof(float), nt, cell_size, &h.ix));  // waits for the stream
+            bufs.free(tab.segtab);
+            bufs.free(tab.Ts);
+        }
+        PCP_TRY(pcp_icp_batch_create(ctx, h.ix, fq, 3 * sizeof(float), nq, seg_offsets, nseg, &h.batch));
+        bufs.free(fq);  // the handle keeps its own copy
+        wait.on = true;
+        PCP_HIP(ctx, hipMemcpyAsync(dpose, pose.data(), pose.size() * sizeof(double), hipMemcpyHostToDevice,
+                                    ctx->stream));
+        double* dstats = dpose + 16 * B;
+        if (trim)
+            PCP_TRY(pcp_icp_batch_run_trimmed_dev(ctx, h.batch, ft, 3 * sizeof(float), nt, dpose, rmax, trim[0],
+                                                  trim[1], trim[2], iters, do_scale, dstats,
+                                                  (uint64_t*)(dstats + 4 * B)));
+        else
+            PCP_TRY(pcp_icp_batch_run_dev(ctx, h.batch, ft, 3 * sizeof(float), nt, dpose, rmax, iters, do_scale,
+                                          dstats));
+        hipError_t e = hipMemcpyAsync(pose.data(), dpose, pose.size() * sizeof(double), hipMemcpyDeviceToHost,
+                                      ctx->stream);
+        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+        wait.on = false;
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return hip_fail(ctx, e, "pcp_get_rot_icp_batch", __FILE__, __LINE__);
+    }
+    for (size_t s = 0; s < B; s++) {
+        double* M = mat_rot + 16 * s;
+        const double* st = stats + 4 * s;
+        if (st[3] > 0) {  // un-centring in pcp_get_rot_icp's order; a segment that never solved: the exact identity
+            std::memcpy(M, pose.data() + 16 * s, 16 * sizeof(double));
+            for (int r = 0; r < 3; r++) {
+                double rcv = M[4 * r] * c[0];
+                rcv = rcv + M[4 * r + 1] * c[1];
+                rcv = rcv + M[4 * r + 2] * c[2];
+                M[4 * r + 3] = (M[4 * r + 3] - rcv) + c[r];
+            }
+        } else {
+            for (int i = 0; i < 16; i++) M[i] = (i % 5 == 0) ? 1.0 : 0.0;
+        }
+        err[s] = (st[0] == 0 && st[3] > 0) ? (float)st[1] : -1.0f;
+        if (steps) steps[s] = (int32_t)st[3];
+        if (kept) {
+            uint64_t row[PCP_ICP_TRIM_STATS];
+            std::memcpy(row, pose.data() + 20 * B + 4 * s, sizeof(row));
+            kept[s] = (int64_t)row[1];
+        }
+    }
+    return PCP_OK;
 }
 
 // pcp_get_rot_icp's staging (joint centroid, fp32 centring, fp32 target index, query set, the

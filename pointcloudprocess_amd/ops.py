@@ -251,6 +251,33 @@ def minmax(ctx, cloud, is_dense=True):
     return np.array(mn[:]), np.array(mx[:])
 
 
+def _seg_args(seg_offsets, T):
+    """(offsets array, nseg, poses array or None) of a span of segments with one 4x4 each (one 4x4
+    for all, or B of them)."""
+    off = [int(v) for v in seg_offsets]
+    if not off:
+        raise ValueError("seg_offsets needs at least one entry")
+    B = len(off) - 1
+    Tm = None
+    if T is not None:
+        T = np.asarray(T, dtype=np.float64)
+        T = np.broadcast_to(T.reshape(1, 16), (B, 16)) if T.size == 16 else T.reshape(B, 16)
+        Tm = (C.c_double * (16 * B))(*np.ascontiguousarray(T).reshape(-1))
+    return (C.c_int64 * len(off))(*off), B, Tm
+
+
+def minmax_segments(ctx, cloud, seg_offsets, T=None, is_dense=True):
+    """(mn, mx), each (B, 4): row s is minmax(transform(cloud[off[s]:off[s + 1]], T[s])) bit for bit,
+    in one pass with no moved copy and one host synchronisation whatever B is (pcp.h V).  T: None
+    (the identity), one 4x4 for all segments, or B of them."""
+    off, B, Tm = _seg_args(seg_offsets, T)
+    mn, mx = (C.c_double * (4 * B))(), (C.c_double * (4 * B))()
+    n = cloud.shape[0]
+    ctx.check(ctx.lib.pcp_minmax_segments_aos48(ctx.h, _ptr(cloud) if n else None, n, off, B, int(is_dense), Tm,
+                                                mn, mx))
+    return np.array(mn[:]).reshape(B, 4), np.array(mx[:]).reshape(B, 4)
+
+
 def centroid(ctx, cloud, is_dense=True):
     c = (C.c_double * 4)()
     cnt = C.c_uint32()
@@ -868,6 +895,29 @@ def get_rot_icp(ctx, src, temp, rmax, iters=20, do_scale=False, cell_size=0.0, s
                                       temp.shape[0], int(temp_dense), M, float(rmax), int(iters),
                                       int(do_scale), float(cell_size), C.byref(err)))
     return float(err.value), np.array(M[:]).reshape(4, 4)
+
+
+def get_rot_icp_batch(ctx, target, frames, seg_offsets, rmax, T0=None, iters=20, do_scale=False, trim=None,
+                      cell_size=0.0, target_dense=True, frames_dense=True):
+    """get_rot_icp for B frames in one call (pcp.h I5d): frames[off[s]:off[s + 1]] moved by T0[s]
+    (None: the identity; one 4x4 for all; or B of them) is registered against target, both (n, 48)
+    records at map coordinates, centred on the target's centroid.  trim = (frac, mult, d_floor) runs
+    the loop with the per-segment point trim.  Returns (err (B,) float32, mats (B, 4, 4), steps (B,)
+    int32, kept (B,) int64 or None without trim); the frame's pose is mats[s] @ T0[s]; err[s] = -1
+    and mats[s] = the identity for a frame that found no pairs."""
+    off, B, Tm = _seg_args(seg_offsets, T0)
+    M = (C.c_double * (16 * B))()
+    err = (C.c_float * B)()
+    steps = (C.c_int32 * B)()
+    kept = (C.c_int64 * B)() if trim is not None else None
+    tr = (C.c_float * 3)(*[float(v) for v in trim]) if trim is not None else None
+    nt, nq = target.shape[0], frames.shape[0]
+    ctx.check(ctx.lib.pcp_get_rot_icp_batch(ctx.h, _ptr(target) if nt else None, nt, int(target_dense),
+                                            _ptr(frames) if nq else None, nq, int(frames_dense), off, B, Tm,
+                                            float(rmax), int(iters), int(do_scale), tr, float(cell_size), M, err,
+                                            steps, kept))
+    return (np.array(err[:], dtype=np.float32), np.array(M[:]).reshape(B, 4, 4), np.array(steps[:], dtype=np.int32),
+            np.array(kept[:], dtype=np.int64) if kept is not None else None)
 
 
 def get_rot_icp_plane(ctx, src, temp, rmax, iters=4, normals_k=16, cell_size=0.0, src_dense=True,
